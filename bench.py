@@ -12,8 +12,13 @@ shard for all 256*N queries, one RCCL all-gather of per-shard (score, id) candid
 then a device merge of each rank's own queries.  Per-GPU work is fixed as N grows
 (256 encodes + 256 x 1M scored rows): "scaling": "weak"; value = 256*N*steps / time.
 
-Rank 0 prints ONE JSON line (plus a roofline object for the dominant kernel and the
-CPU baseline - the oracle restatement timed on this host's cores on a bounded sample).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps steps of the
+headline arithmetic and prints that figure with the per-kernel times and rooflines read
+from those same steps.  --full adds everything else to the line, each a run of its own:
+the planted-query parity guard, the other arithmetics, BASELINE configs 2 / 4 / 5, the
+single-query latencies, the clustered corpus, the LangChain leg and the CPU baseline (the
+oracle restatement timed on this host's cores on a bounded sample).  --dump-outputs DIR
+writes what the last timed step returned as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -74,7 +79,25 @@ def parse():
                    help="skip the config-2, clustered-corpus, long-query and k=50 extras")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-threads", type=int, default=int(os.environ.get("OMP_NUM_THREADS", "0") or 0))
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline: the parity guard, the other arithmetics, "
+                        "configs 2 / 4 / 5, single-query latencies, the extras and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs (scores, ids, embeddings) as DIR/<name>.npy")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy of the last timed step's outputs: float32 as computed, the int64 row
+    ids as float64 (exact below 2^53).  A few hundred KB at the bench's sizes."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"),
+                a.astype(np.float32 if a.dtype == np.float32 else np.float64))
 
 
 def encoder_flops(cfg, B, L):
@@ -533,12 +556,13 @@ def main():
         return s, i
 
     # parity guard at full size: planted queries find their rows (property check)
-    pq, planted = synth.queries_device(64, full)
     ok_planted = {}
-    for name, (_, prec) in PRECISIONS.items():
-        index.set_precision(prec)
-        _, pq_i = searcher.search(pq, K) if world > 1 else local_search(pq, K)
-        ok_planted[name] = bool((pq_i[:32, 0] == planted[:32]).all())
+    if args.full:
+        pq, planted = synth.queries_device(64, full)
+        for name, (_, prec) in PRECISIONS.items():
+            index.set_precision(prec)
+            _, pq_i = searcher.search(pq, K) if world > 1 else local_search(pq, K)
+            ok_planted[name] = bool((pq_i[:32, 0] == planted[:32]).all())
     del full
     torch.cuda.empty_cache()
 
@@ -563,12 +587,14 @@ def main():
             searcher.timings = []  # HIP events around each collective (host time for gloo)
         t0 = time.perf_counter()
         for it in range(args.steps):
-            step(evs[it])
+            s_last, i_last = step(evs[it])
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        # what the last timed step handed back (later runs reuse the buffers)
+        last = {"scores": s_last[:B].clone(), "ids": i_last[:B].clone(), "embeddings": q.clone()}
         coll = None
         if world > 1:
             coll = {}
@@ -585,13 +611,34 @@ def main():
         stage_ms.update({k: v / args.steps for k, v in index.read_timing().items()})
         enc.set_timing(False)
         index.set_timing(False)
-        return {"elapsed": elapsed, "stage_ms": stage_ms, "collectives": coll,
+        return {"elapsed": elapsed, "stage_ms": stage_ms, "collectives": coll, "last": last,
                 "screen_fallbacks": index.screen_fallbacks - fb0,
                 "screen_passdowns": index.screen_passdowns - pd0,
                 "enc_ms": statistics.mean(e[0].elapsed_time(e[1]) for e in evs),
                 "srch_ms": statistics.mean(e[1].elapsed_time(e[2]) for e in evs)}
 
-    runs = {name: measure(precs) for name, precs in PRECISIONS.items()}
+    HEAD = "f32x6_screen"
+    if args.full:
+        runs = {name: measure(precs) for name, precs in PRECISIONS.items()}
+    else:
+        # set-up the other runs otherwise do: untimed steps build the index's shadow slabs
+        # and the encoder's pre-split weights, whatever --warmup is, the last ones on the
+        # per-kernel timeline the timed steps run with
+        enc.set_precision(PRECISIONS[HEAD][0])
+        index.set_precision(PRECISIONS[HEAD][1])
+        step()
+        enc.set_timing(True)
+        index.set_timing(True)
+        for _ in range(3):
+            step()
+        torch.cuda.synchronize()
+        enc.set_timing(False)
+        index.set_timing(False)
+        runs = {HEAD: measure(PRECISIONS[HEAD])}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, runs[HEAD]["last"])
+    for r in runs.values():
+        del r["last"]
     # the headline configuration for everything after (the few-row single-query forward is
     # fp32 whatever the precision)
     enc.set_precision(_lib.MQ_DTYPE_F32X6)
@@ -601,7 +648,7 @@ def main():
     # (k=50 -> max(2k,50) capped at 64) + exact fp32 re-rank; search only, same queries,
     # recall@50 against the exact fp32 scan ---------------------------------------------
     cfg5 = None
-    if world == 1:
+    if world == 1 and args.full:
         k5 = 50
         s5 = torch.empty((B, k5), dtype=torch.float32, device=dev)
         i5 = torch.empty((B, k5), dtype=torch.int64, device=dev)
@@ -627,7 +674,7 @@ def main():
 
     # ---- SURVEY.md §8d secondary run: the same step at L = 128 (headline arithmetic) ----
     sec = None
-    if world == 1 and args.secondary_seq_len > 0:
+    if world == 1 and args.full and args.secondary_seq_len > 0:
         L2 = args.secondary_seq_len
         ids2_np, mask2_np = synth.token_batch(B, L2, seed=synth.TOKEN_SEED)
         ids2, mask2 = torch.from_numpy(ids2_np).to(dev), torch.from_numpy(mask2_np).to(dev)
@@ -654,7 +701,7 @@ def main():
 
     # ---- single-query latency (embed 1 query + search the shard), exact f32 ----------
     lat, lat_parts, single_roof = [], None, None
-    if world == 1 and args.single_iters > 0:
+    if world == 1 and args.full and args.single_iters > 0:
         ids1, mask1, q1 = ids[:1].contiguous(), mask[:1].contiguous(), q[:1]
         pd0 = index.screen_passdowns
         for it in range(args.single_iters + 5):
@@ -704,10 +751,10 @@ def main():
                        "traffic": (traffic_db_early.get("i8_thresh_kernel", 0) + traffic_db_early.get("i8_thresh_sample", 0))
                        or None}
 
-    c4 = config4(args, enc, world, rank, dev, backend) if args.config4_steps > 0 else None
+    c4 = config4(args, enc, world, rank, dev, backend) if args.full and args.config4_steps > 0 else None
 
     extras = {}
-    if world == 1 and not args.no_extras:
+    if world == 1 and args.full and not args.no_extras:
         extras["exact_k50_batch"] = exact_k50(index, q, dev)
         extras["long_query_p50"] = long_queries(args, enc, index, dev, K)
         extras["config2"] = config2(args, enc, dev, ids, mask, q)
@@ -806,13 +853,10 @@ def main():
                 "ms_per_step": round(r["elapsed"] / args.steps * 1e3, 3),
                 "roofline": roof, "search_roofline": search_roof,
                 "encoder_ms": round(r["enc_ms"], 3), "search_ms": round(r["srch_ms"], 3),
-                "kernels": kernels, "planted_top1_ok": ok_planted[name],
+                "kernels": kernels, "planted_top1_ok": ok_planted.get(name),
                 "screen_fallbacks": r["screen_fallbacks"], "screen_passdowns": r["screen_passdowns"]}
 
-    main_r = summarize("f32x6_screen", runs["f32x6_screen"])
-    exact_r = summarize("f32", runs["f32"])
-    direct_r = summarize("f32_direct_search", runs["f32_direct_search"])
-    alt_r = summarize("f32x6", runs["f32x6"])
+    main_r = summarize(HEAD, runs[HEAD])
     out = {
         "metric": "queries/s (embed+top-k, k=5, b=256) over 1M×768 corpus; p50 single-query ms",
         "value": main_r["value"], "unit": "queries/s", "n_gpus": world, "steps": args.steps,
@@ -839,15 +883,21 @@ def main():
                        "re-rank, certified bound per query; uncertified queries re-run on the split-f32 "
                        "screen (%d in the timed steps) or the direct exact scan (%d)"
                        % (main_r["screen_passdowns"], main_r["screen_fallbacks"]),
-        "exact_f32_encoder": dict(
+        "full": args.full,  # False: the keys --full measures in runs of their own are null
+        "exact_f32_encoder": None, "f32_direct_search": None, "split_f32": None,
+    }
+    if args.full:
+        exact_r = summarize("f32", runs["f32"])
+        direct_r = summarize("f32_direct_search", runs["f32_direct_search"])
+        alt_r = summarize("f32x6", runs["f32x6"])
+        out["exact_f32_encoder"] = dict(
             {kk: exact_r[kk] for kk in ("value", "ms_per_step", "encoder_ms", "search_ms", "roofline",
                                         "kernels", "planted_top1_ok", "screen_fallbacks", "screen_passdowns")},
-            dtype="f32 (encoder on the exact f32 MFMA, v_mfma_f32_32x32x2_f32; exact fp32 top-k)"),
-        "f32_direct_search": {kk: direct_r[kk] for kk in ("value", "ms_per_step", "search_ms",
-                                                          "search_roofline", "planted_top1_ok")},
-        "split_f32": dict(alt_r, dtype="f32 via exact 3-way bf16 split (6 bf16 MFMAs / product, "
-                                       "fp32 accumulate) for the encoder and the direct scan"),
-    }
+            dtype="f32 (encoder on the exact f32 MFMA, v_mfma_f32_32x32x2_f32; exact fp32 top-k)")
+        out["f32_direct_search"] = {kk: direct_r[kk] for kk in ("value", "ms_per_step", "search_ms",
+                                                                "search_roofline", "planted_top1_ok")}
+        out["split_f32"] = dict(alt_r, dtype="f32 via exact 3-way bf16 split (6 bf16 MFMAs / product, "
+                                             "fp32 accumulate) for the encoder and the direct scan")
     out["distributed"] = dist_info
     # which library ran: the source hash compiled into it, and whether it is this tree's
     built = _lib.built_source_hash()
@@ -862,7 +912,7 @@ def main():
     out["secondary_long_queries"] = sec
     out["screen_counters_whole_run"] = run_counters
     out.update(extras)
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         def corpus_host():
             return torch.nn.functional.normalize(
                 synth.corpus_device(args.corpus_rows, 768, dev), dim=1).cpu().numpy()

@@ -4,5 +4,5 @@
 set -o pipefail
 mkdir -p gpurun_out
 MQ_DIST_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 3 --warmup 1 \
+  --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 3 --warmup 1 --full \
   --no-cpu-baseline --single-iters 5 > gpurun_out/bench_n2.json 2> gpurun_out/bench_n2.err
