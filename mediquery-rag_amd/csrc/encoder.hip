@@ -205,6 +205,19 @@ __global__ __launch_bounds__(T::THREADS, T::WG_PER_CU) void gemm_nt_kernel(const
     int64_t n0l;
     coords(i, m0, n0l);
     const int n0 = (int)n0l;
+    if constexpr (T::M16) {  // 16x16 accumulator blocks (F32Tile::M16): K2p's store
+      static_assert(EPI != EPI_RESID_STATS, "no LayerNorm partials on the 16x16x32 tiles");
+      floatx4 a4[2 * T::TM][2 * T::TN];
+#pragma unroll
+      for (int m = 0; m < 2 * T::TM; ++m)
+#pragma unroll
+        for (int n = 0; n < 2 * T::TN; ++n)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) a4[m][n][e] = acc[m >> 1][n >> 1][4 * (2 * (m & 1) + (n & 1)) + e];
+      store_wave_tile16<EPI, 2 * T::TM, 2 * T::TN>(a4, m0 + wm * T::WM, n0 + wn * T::WN, M, N, bias, resid, ldr, out,
+                                                   ldo, lane);
+      return;
+    }
     if constexpr (EPI == EPI_RESID_STATS) {
       // y = acc + bias + resid, then per row the partial (mean, M2) of y over the wave
       // tile's WN = kLnPartW columns: the 32 lanes of a lane half hold a row's columns
@@ -1756,9 +1769,11 @@ using GemmSmall = F32Tile<1, 4, 1, 1>;  // 32 x 128  (few rows)
 // so a grid that is not a multiple of 2*CUs idles part of the chip in its last round
 // (M = 8192: N = 768 -> 128x96 gives exactly 512 tiles; 2304 -> 1536).  Cost model:
 // rounds * tile area / relative tile efficiency.
-using X6Big = F32Tile<2, 2, 2, 2, true>;  // 128 x 128, split-f32
-using X6T96 = F32Tile<4, 1, 1, 3, true>;  // 128 x 96
-using X6Mid = F32Tile<2, 2, 2, 1, true>;  // 128 x 64
+// (the encoder's split-f32 tiles take K2p's arithmetic: the 16x16x32 MFMA, F32Tile::M16)
+using X6Big = F32Tile<2, 2, 2, 2, true, 2, false, 0, false, true>;  // 128 x 128, split-f32
+using X6T96 = F32Tile<4, 1, 1, 3, true, 2, false, 0, false, true>;  // 128 x 96
+using X6Mid = F32Tile<2, 2, 2, 1, true, 2, false, 0, false, true>;  // 128 x 64
+using X6W192 = F32Tile<4, 2, 1, 3, true, 2, false, 0, false, true>;  // 128 x 192, 8 waves
 
 // Tile codes (also the mq_debug_gemm_f32 `tile` argument): 0-3 exact f32 128x128 /
 // 128x96 / 128x64 / 32x128, 4 split-K (host path only), 5-7 split-f32 128x128 / 128x96
@@ -1774,7 +1789,7 @@ void launch_gemm_tile(const GemmArgs& g, int tile, int num_cus, hipStream_t s) {
     case 6: launch_gemm_t<X6T96, EPI>(g, num_cus, s); return;
     case 7: launch_gemm_t<X6Mid, EPI>(g, num_cus, s); return;
     case 8: launch_gemm_t<F32Tile<4, 2, 1, 3>, EPI>(g, num_cus, s); return;         // 128x192, 8 waves
-    case 9: launch_gemm_t<F32Tile<4, 2, 1, 3, true>, EPI>(g, num_cus, s); return;   // x6 128x192
+    case 9: launch_gemm_t<X6W192, EPI>(g, num_cus, s); return;                       // x6 128x192
     default: launch_gemm_t<GemmSmall, EPI>(g, num_cus, s); return;
   }
 }

@@ -108,4 +108,62 @@ __device__ __forceinline__ void store_wave_tile(floatx16 (&acc)[TM][TN], int wr0
   }
 }
 
+// The same store for a wave's MB x NB grid of 16x16 accumulators (v_mfma_f32_16x16x32_*:
+// register e of lane l is row 4 (l >> 4) + e, column l & 15 of its block).  The residual
+// is loaded one block row at a time (the caller's operand fragments stay live across it).
+template <int EPI, int MB, int NB>
+__device__ __forceinline__ void store_wave_tile16(floatx4 (&acc)[MB][NB], int wr0, int wc0, int M, int N,
+                                                  const float* __restrict__ bias, const float* __restrict__ resid,
+                                                  int ldr, float* __restrict__ out, int ldo, int lane) {
+  const int c = lane & 15, g = lane >> 4;
+  if (wr0 + MB * 16 <= M && wc0 + NB * 16 <= N) {
+    float bv[NB];
+#pragma unroll
+    for (int n = 0; n < NB; ++n) bv[n] = bias[wc0 + n * 16 + c];
+    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(resid + (EPI == EPI_RESID ? (int64_t)wr0 * ldr + wc0 : 0)), (short)0, 0x7fffffff, 0x00020000);
+    const int rl = (4 * g * ldr + c) * 4;
+    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(out + (int64_t)wr0 * ldo + wc0), (short)0, 0x7fffffff, 0x00020000);
+    const int ol = (4 * g * ldo + c) * 4;
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+      float rv[NB][4];
+      if constexpr (EPI == EPI_RESID) {
+#pragma unroll
+        for (int n = 0; n < NB; ++n)
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            rv[n][e] = __uint_as_float(
+                __builtin_amdgcn_raw_buffer_load_b32(rr, rl, ((m * 16 + e) * ldr + n * 16) * 4, 0));
+      }
+#pragma unroll
+      for (int n = 0; n < NB; ++n)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          float v = epi_apply<EPI>(acc[m][n][e] + bv[n]);
+          if constexpr (EPI == EPI_RESID) v += rv[n][e];
+          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), ro, ol, ((m * 16 + e) * ldo + n * 16) * 4, 0);
+        }
+    }
+    return;
+  }
+#pragma unroll
+  for (int n = 0; n < NB; ++n) {
+    const int col = wc0 + n * 16 + c;
+    if (col >= N) continue;
+    const float b = bias[col];
+#pragma unroll
+    for (int m = 0; m < MB; ++m)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int row = wr0 + m * 16 + 4 * g + e;
+        if (row >= M) continue;
+        float v = epi_apply<EPI>(acc[m][n][e] + b);
+        if constexpr (EPI == EPI_RESID) v += resid[(int64_t)row * ldr + col];
+        out[(int64_t)row * ldo + col] = v;
+      }
+  }
+}
+
 }  // namespace mq

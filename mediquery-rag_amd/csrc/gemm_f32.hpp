@@ -17,7 +17,9 @@
 //    relative, i.e. fp32-class results at 16/6 = 2.67x the f32 MFMA rate.  K is staged
 //    in 16-wide slices; an LDS row holds the three planes [3][16] bf16 + 16 B pad
 //    (112-B rows: slot = 7*row + 2*plane + h mod 16, conflict-free); lane half h carries
-//    k = 8h + j.
+//    k = 8h + j.  The encoder's split-f32 tiles set M16: the same six products on
+//    v_mfma_f32_16x16x32_bf16 (32-wide slices, 208-B rows of three 64-B planes, 16x16
+//    accumulator blocks), the arithmetic of K2p (gemm_x6p.hip), bit for bit.
 //
 //  * 256 or 512 threads = 4 or 8 waves laid out WAVES_M x WAVES_N; each wave owns
 //    TM x TN MFMA tiles of 32x32 (f32x16 accumulators, 16 regs/lane each).
@@ -35,10 +37,16 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
 
 template <int WAVES_M_, int WAVES_N_, int TM_, int TN_, bool X6_ = false, int PF_ = 2,
-          bool BF16_ = false, int BK_ = 0, bool NTB_ = false>
+          bool BF16_ = false, int BK_ = 0, bool NTB_ = false, bool M16_ = false>
 struct F32Tile {
   static constexpr int WAVES_M = WAVES_M_, WAVES_N = WAVES_N_, TM = TM_, TN = TN_;
   static constexpr bool X6 = X6_;
+  // M16 (split f32 only; the encoder's x6 tiles, the restatement of K2p's arithmetic): the
+  // six products on v_mfma_f32_16x16x32_bf16 - 32-deep slices, each 32x32 accumulator as
+  // four 16x16 blocks (register 4 (2 sm + sn) + e = row 16 sm + 4 (lane >> 4) + e, column
+  // 16 sn + (lane & 15)), lane (c = lane & 15, kq = lane >> 4) carrying k = 8 kq + j
+  static constexpr bool M16 = M16_;
+  static_assert(!M16 || X6, "the 16x16x32 form is a split-f32 option");
   // NTB: B-operand loads are non-temporal (the single-query split-K GEMMs of the layers past
   // the encoder's resident_layers: their weights stream once and should not evict the
   // resident layers' weights from MALL)
@@ -55,19 +63,21 @@ struct F32Tile {
   static constexpr int ROWS = BM + BN;
   // K per staged slice: 32 (exact f32 / bf16 default), 16 (split f32; or an exact-f32 tile
   // whose B panel is too tall for two 32-deep stages, e.g. the full-row 32 x 768 tile)
-  static constexpr int BK = BK_ ? BK_ : (X6 ? 16 : 32);
+  static constexpr int BK = BK_ ? BK_ : (X6 && !M16 ? 16 : 32);
   static_assert(BK == 32 || (BK == 16 && !BF16), "slice depth 32, or 16 for the f32 forms");
   static constexpr int F4_PER_ROW = BK / 4;               // float4 per row per slice
   // LDS row stride in 4-B words: 144-B rows at BK 32, 80-B rows at BK 16 (16 rows of one
   // ds_read_b128 group still land in distinct 16-B bank groups), 112-B split-plane rows
-  static constexpr int ROW_FLOATS = X6 ? 28 : BK + 4;
+  // (M16: three 64-B planes + 16 B pad, 208-B rows)
+  static constexpr int ROW_FLOATS = X6 ? (M16 ? 52 : 28) : BK + 4;
   static constexpr int TOTAL_F4 = ROWS * F4_PER_ROW;                  // float4 per slice
   static constexpr int LOADS = (TOTAL_F4 + THREADS - 1) / THREADS;      // per thread
   static constexpr bool PARTIAL = TOTAL_F4 % THREADS != 0;              // last slot ragged
   static constexpr int STAGE_FLOATS = ROWS * ROW_FLOATS;
   static_assert(THREADS == 256 || THREADS == 512, "4- or 8-wave workgroups");
   // workgroups per CU the kernel is built for: 2 x 4 waves, or 1 x 8 waves (LDS)
-  static constexpr int WG_PER_CU = THREADS == 256 ? 2 : 1;
+  // (an M16 tile's two 32-deep stages of 208-B rows take 91-104 KB: one per CU)
+  static constexpr int WG_PER_CU = THREADS == 256 && !M16 ? 2 : 1;
   static_assert(BM % 32 == 0 && BN % 32 == 0, "block tile must be a multiple of 32");
   // A rows fill whole load slots (compile-time A / B split) unless the A panel is smaller
   // than one slot (the full-row 32 x H tile: 128 A float4 for 512 threads), then per thread
@@ -177,7 +187,7 @@ struct Stager {
         split3(r[i], pl);
         char* base = reinterpret_cast<char*>(stage + row * T::ROW_FLOATS) + ch * 8;
 #pragma unroll
-        for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2*>(base + p * 32) = pl[p];
+        for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2*>(base + p * (T::BK * 2)) = pl[p];
       } else {
         *reinterpret_cast<floatx4*>(stage + row * T::ROW_FLOATS + ch * 4) = r[i];
       }
@@ -220,6 +230,42 @@ __device__ __forceinline__ void mma_slice(const float* stage, floatx16 (&acc)[T:
           acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[c][tm], b[c][tn], acc[tm][tn], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
+    return;
+  }
+  if constexpr (T::X6 && T::M16) {
+    // lane (c, kq): k = 8 kq .. 8 kq + 7 of this 32-wide slice, one ds_read_b128 per plane
+    // and 16-row block; per 16x16 block the six products in K2p's order
+    const int c = lane & 15, kq = lane >> 4;
+    const char* as = reinterpret_cast<const char*>(stage + (wm * T::WM + c) * T::ROW_FLOATS) + kq * 16;
+    const char* bs = reinterpret_cast<const char*>(stage + (T::BM + wn * T::WN + c) * T::ROW_FLOATS) + kq * 16;
+    bf16x8 a[2 * T::TM][3], b[2 * T::TN][3];
+#pragma unroll
+    for (int m = 0; m < 2 * T::TM; ++m)
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+        a[m][p] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uintx4*>(as + m * 16 * T::ROW_FLOATS * 4 + p * 64));
+#pragma unroll
+    for (int n = 0; n < 2 * T::TN; ++n)
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+        b[n][p] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uintx4*>(bs + n * 16 * T::ROW_FLOATS * 4 + p * 64));
+#pragma unroll
+    for (int m = 0; m < 2 * T::TM; ++m)
+#pragma unroll
+      for (int n = 0; n < 2 * T::TN; ++n) {
+        floatx16& full = acc[m >> 1][n >> 1];
+        const int q = 4 * (2 * (m & 1) + (n & 1));
+        floatx4 d = {full[q], full[q + 1], full[q + 2], full[q + 3]};
+        // smallest terms first
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m][2], b[n][0], d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m][1], b[n][1], d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m][0], b[n][2], d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m][1], b[n][0], d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m][0], b[n][1], d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m][0], b[n][0], d, 0, 0, 0);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) full[q + e] = d[e];
+      }
     return;
   }
   if constexpr (T::X6) {

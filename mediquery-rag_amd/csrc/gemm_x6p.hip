@@ -5,21 +5,36 @@
 // out[M,N] = epi(A[M,K] . W[N,K]^T + bias (+ resid)), A fp32, W as W3 (3 bf16 planes).
 //
 //  * one 512-thread workgroup per CU (8 waves, two per SIMD), persistent over tiles;
-//    block tile BM x BN = (WAVES_M 32 TM) x (WAVES_N 32 TN), wave tile TM x TN 32x32 MFMAs;
-//  * K advances in 16-deep stages through an NBUF-slot LDS ring filled by LDS-DMA
-//    (global_load_lds_dwordx4, no VGPR round trip, no staging VALU): NBUF - 1 stages in
-//    flight while one is multiplied, a counted vmcnt and one s_barrier per stage;
-//  * W3 stage: BN / 32 x 3 fragments of 1 KB, each one DMA wave-instruction, read back by
-//    one ds_read_b128 per lane in lane order (conflict-free by construction);
-//  * A stage: BM rows x 16 fp32 (64 B per row), 16 rows per DMA wave-instruction; the four
-//    16-B chunks of row R sit at slot c ^ ((R >> 2) & 3) (the XOR goes on the DMA SOURCE
-//    address: the DMA destination is lane-linear), which makes the A-fragment
-//    ds_read_b128 (lane half h: chunks 2h, 2h + 1 of row r) conflict-free;
-//  * A fragments are split into their three bf16 planes in registers right after the
-//    read (split3: round-to-nearest per plane, residuals exact) - VALU that issues in the
-//    MFMA shadow - and each 32x32 output tile takes the six products a2b0, a1b1, a0b2,
-//    a1b0, a0b1, a0b0 per 16-deep step in the order of gemm_f32.hpp's x6 tiles: the same
-//    operands in the same order, so the results are bit-identical to those tiles;
+//    block tile BM x BN = (WAVES_M 32 TM) x (WAVES_N 32 TN); a wave owns a 32 TM x 32 TN
+//    tile as 2 TM x 2 TN accumulator blocks of v_mfma_f32_16x16x32_bf16 (X6pTile::M16,
+//    every tile code below 16);
+//  * K advances in 32-deep stages - two 16-deep sub-stages - through an NBUF-slot LDS ring
+//    filled by LDS-DMA (global_load_lds_dwordx4, no VGPR round trip, no staging VALU), a
+//    counted vmcnt and one s_barrier per stage; on the default tiles 4 loader waves issue
+//    the DMAs beside 4 compute waves;
+//  * W3 sub-stage: BN / 32 x 3 fragments of 1 KB, each one DMA wave-instruction.  Lane
+//    (c = lane & 15, kq = lane >> 4) of a 16x16x32 operand holds k = 8 kq + j of row c: for
+//    the 16-row half s of a fragment it reads the 16 B at (kq & 1) 512 + (16 s + c) 16 of
+//    sub-stage kq >> 1 (each group of lanes the LDS serves together covers 16 distinct
+//    16-B slots: conflict-free);
+//  * A sub-stage: BM rows x 16 fp32 (64 B per row), 16 rows per DMA wave-instruction; the
+//    four 16-B chunks of row R sit at slot chunk ^ g((R >> 2) & 3), g = {0, 1, 3, 2} (the
+//    XOR goes on the DMA SOURCE address: the DMA destination is lane-linear).  The lane
+//    reads chunks 2 (kq & 1), + 1 of row c of sub-stage kq >> 1.  ds_read_b128 is served in
+//    the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32; with g
+//    every group reads 16 distinct 16-B slots, for this read and for the 32x32x16 one
+//    (with the plain (R >> 2) & 3 the 16x16x32 read was 2-way: lanes 0-3 against 24-27);
+//  * A fragments are split into their three bf16 planes in registers (split3: round to
+//    nearest per plane, residuals exact), in sub-pieces of at most 2 VALU in the MFMA
+//    gaps, and each 16x16 block takes the six products a2b0, a1b1, a0b2, a1b0, a0b1, a0b0
+//    per 32-deep step: the operands and order of gemm_f32.hpp's M16 tiles, so the results
+//    are bit-identical to those tiles;
+//  * operands are single-buffered and reloaded in place (the M16 branch of
+//    gemm_x6p_kernel has the slot plan);
+//  * tile codes 16 / 17 keep the former k-step (v_mfma_f32_32x32x16_bf16 on 32x32 blocks,
+//    16-deep stages, 4 ring slots, fragments double-buffered) to re-measure the two MFMA
+//    shapes in one library; the chip holds a higher clock on 16x16x32 (1.13-1.16x at the
+//    encoder's shapes);
 //  * tiles are walked in GM-row bands (GM row tiles x all column tiles, column-major
 //    inside a band), each XCD taking consecutive tiles: at M = 8192 an XCD's 32 CUs share
 //    4 A row panels and 8 W3 column panels in its L2.
@@ -48,6 +63,9 @@ __device__ __forceinline__ void x6p_glds(const void* base, unsigned voff, unsign
                : "v"(voff), "s"(base), "s"(__builtin_amdgcn_readfirstlane(lds_dst))
                : "memory");
 }
+
+// g of the A stage's chunk swizzle (file header): {0, 1, 3, 2}
+__device__ __forceinline__ int a_swz(int q) { return q ^ (q >> 1); }
 
 // Exact 3-way bf16 split of 4 floats (gemm_f32.hpp's split3, same arithmetic) with the
 // packing conversion as a compiler-visible fptrunc (v_cvt_pk_bf16_f32, round to nearest
@@ -84,7 +102,8 @@ __device__ __forceinline__ void split3v(floatx4 x, uint2 (&pl)[3]) {
 #endif
 
 template <int WAVES_M_, int WAVES_N_, int TM_, int TN_, int NBUF_, int KS_ = 1, int DMAW_ = 8, bool SCHED_ = false,
-          int DBG_ = 0, int DSTEP_ = 1, int BR0_ = 0, int PS_ = 4, bool LDR_ = false>
+          int DBG_ = 0, int DSTEP_ = 1, int BR0_ = 0, int PS_ = 4, bool LDR_ = false, bool M16_ = false,
+          bool DEEP_ = false>
 struct X6pTile {
   static constexpr int WAVES_M = WAVES_M_, WAVES_N = WAVES_N_, TM = TM_, TN = TN_, NBUF = NBUF_;
   static constexpr int KS = KS_;    // 16-deep k-steps per LDS stage (one barrier per stage)
@@ -105,6 +124,13 @@ struct X6pTile {
   // issue the stage DMAs (an LDS-DMA holds the issuing wave for ~60-185 cycles; a loader
   // wave pays that beside its SIMD's compute wave, whose MFMA stream it never interrupts)
   static constexpr bool LDR = LDR_;
+  // M16 (the product tiles): the k-step on v_mfma_f32_16x16x32_bf16 - the wave's
+  // TM x TN 32x32 blocks as 2 TM x 2 TN 16x16 blocks, one 32-deep step per stage (KS = 2),
+  // same LDS image, same LDS read bytes and split VALU per unit of K (the M16 branch of
+  // gemm_x6p_kernel).
+  // DEEP: the ring runs NBUF stages ahead (every read of a stage is in the iteration
+  // before the one that multiplies it; the barrier then waits for those reads).
+  static constexpr bool M16 = M16_, DEEP = DEEP_;
   static constexpr int NW = WAVES_M * WAVES_N, THREADS = (LDR ? 2 * NW : NW) * 64;
   static constexpr int WM = TM * 32, WN = TN * 32, BM = WAVES_M * WM, BN = WAVES_N * WN;
   static constexpr int A_SUB = BM * 64;  // one k-step of A: 16 fp32 per row
@@ -118,13 +144,15 @@ struct X6pTile {
   // stage issue distance: a stage's slot is free once its last k-step's fragments are in
   // registers - at KS = 1 that happens one iteration early (the fragments run one k-step
   // ahead), so the ring can run one stage further ahead
-  static constexpr int AHEAD = KS == 1 ? NBUF : NBUF - 1;
+  static constexpr int AHEAD = KS == 1 || (M16 && DEEP) ? NBUF : NBUF - 1;
+  static_assert(!M16 || (KS == 2 && SCHED), "16x16x32 body: slot-scheduled 32-deep stages");
+  static_assert(!DEEP || M16, "DEEP is a 16x16x32 option");
 #ifndef MQ_X6P_GM  // tuning default: 8 row tiles per band (half the W3 column blocks per XCD
 #define MQ_X6P_GM 4  // round) measured the same at every headline shape (tools/gpu_ab_x6p.sh)
 #endif
   static constexpr int GM = MQ_X6P_GM;  // row tiles per band of the tile walk
   static_assert(LDR ? NW == 4 : NW == 8, "8-wave workgroups");
-  static_assert(!SCHED || (CNT_HI - 1) * DSTEP < TM * TN * 6, "DMAs per k-step slots");
+  static_assert(!SCHED || (CNT_HI - 1) * DSTEP < TM * TN * 6 * (M16 ? 4 : 1), "DMAs per k-step slots");
   static_assert(AHEAD >= 2 && NBUF * STAGE <= 160 * 1024, "LDS ring");
 };
 
@@ -182,8 +210,8 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
   // 16 ins' .. + 15 (ins' < NA) or W3 fragment ins' - NA = 3 (column block) + plane.
   int is_j = 0, is_i = 0, is_kt = 0, is_m0, is_n0;
   coords(0, is_m0, is_n0);
-  // A chunk this lane moves: row 16 ins + (lane >> 2), slot lane & 3 -> chunk slot ^ ((row >> 2) & 3)
-  const unsigned a_chunk = (unsigned)(((lane & 3) ^ ((lane >> 4) & 3)) * 16);
+  // A chunk this lane moves: row 16 ins + (lane >> 2), slot lane & 3 -> chunk slot ^ g((row >> 2) & 3)
+  const unsigned a_chunk = (unsigned)(((lane & 3) ^ a_swz((lane >> 4) & 3)) * 16);
   // DMA t (< CNT_HI) of this wave for the stage at is_j into slot `buf`
   auto issue_one = [&](int buf, int t) __attribute__((always_inline)) {
     if constexpr (T::DBG & 1) return;
@@ -228,7 +256,7 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
 
   // ---- fragments of one k-step (A split into its planes after the read) and its MFMAs:
   // the six products per 32x32 tile
-  const int r = lane & 31, h = lane >> 5, sw = (r >> 2) & 3;
+  const int r = lane & 31, h = lane >> 5, sw = a_swz((r >> 2) & 3);
   const unsigned a_lo = (unsigned)((((2 * h) ^ sw) * 16)), a_hi = (unsigned)((((2 * h + 1) ^ sw) * 16));
   struct Frags {
     floatx4 raw[T::TM][2];  // A fragment as read (fp32 k = 8h .. 8h + 7)
@@ -418,6 +446,124 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
 #pragma unroll
     for (int d = 0; d < T::AHEAD; ++d) issue(d);
   }
+  if constexpr (T::M16) {
+    // ---- the k-step on v_mfma_f32_16x16x32_bf16 (compute waves; SCHED, loader waves).
+    // The wave tile is MB x NB16 16x16 blocks; one step is a whole 32-deep stage: lane
+    // (c = lane & 15, kq = lane >> 4) holds k = 8 kq + j of row / column c of a block, i.e.
+    // 16-deep sub-stage kq >> 1, half kq & 1 of the fragments the 32x32x16 body reads.
+    // Operands are single-buffered and reloaded in place.  Slot i = 36 m + 6 n + t is
+    // product t of block (m, n): the step walks the A row blocks (region m = 36 slots)
+    // over all B column blocks.  Region m splits, in sub-pieces of <= 2 VALU per slot, A
+    // block m - 1 of the NEXT step (block MB - 1 of this step in region 0) out of `raw`,
+    // then reads block m of the next step into `raw`; the last region reloads each B
+    // fragment of the next step right behind its last product.  Every read of stage
+    // j + 1 is issued in iteration j.
+    constexpr int MB = 2 * T::TM, NB16 = 2 * T::TN, RS = NB16 * 6, NM16 = MB * RS, NSUB = 28;
+    static_assert(RS >= NSUB + 4, "a region holds one block's split and its raw reads");
+    const int c = lane & 15, kq = lane >> 4, hq = kq & 1, sw16 = a_swz((c >> 2) & 3);
+    const unsigned a_base = (unsigned)((kq >> 1) * T::A_SUB + (wm * T::WM + c) * 64);
+    const unsigned a_lo16 = a_base + (unsigned)(((2 * hq) ^ sw16) * 16);
+    const unsigned a_hi16 = a_base + (unsigned)(((2 * hq + 1) ^ sw16) * 16);
+    const unsigned b_base =
+        (unsigned)(T::KS * T::A_SUB + (kq >> 1) * T::B_SUB + wn * T::TN * 3 * 1024 + hq * 512 + c * 16);
+    floatx4 acc4[MB][NB16];
+    uintx4 au[MB][3];
+    bf16x8 bw[NB16][3];
+    floatx4 raw[2];  // chunks 2 hq, 2 hq + 1 of the block being split
+    auto rd_raw = [&](const unsigned char* st, int m, int half) __attribute__((always_inline)) {
+      raw[half] = *reinterpret_cast<const floatx4*>(st + m * 1024 + (half ? a_hi16 : a_lo16));
+    };
+    auto rd_b = [&](const unsigned char* st, int n, int p) __attribute__((always_inline)) {
+      bw[n][p] = __builtin_bit_cast(
+          bf16x8, *reinterpret_cast<const uintx4*>(st + b_base + ((n >> 1) * 3 + p) * 1024 + (n & 1) * 256));
+    };
+    // sub-piece q < NSUB of the split of `raw` into au[m]: per half, planes 0 and 1 of the
+    // x,y and z,w pairs as (convert) (residual lo) (residual hi), then plane 2's converts
+    auto sub = [&](int m, int q) __attribute__((always_inline)) {
+      const int half = q / 14, rq = q % 14;
+      const int p = rq < 12 ? rq / 6 : 2, part = rq < 12 ? (rq % 6) / 3 : rq - 12, op = rq < 12 ? rq % 3 : 0;
+      floatx4& x = raw[half];
+      if (op == 0) {
+        unsigned u = cvt_pk_bf16(x[2 * part], x[2 * part + 1]);
+        asm volatile("" : "+v"(u));
+        au[m][p][2 * half + part] = u;
+      } else {
+        const unsigned u = au[m][p][2 * half + part];
+        if (op == 1)
+          x[2 * part] -= bf16_lo(u);
+        else
+          x[2 * part + 1] -= bf16_hi(u);
+        asm volatile("" : "+v"(x));
+      }
+    };
+    auto zero4 = [&]() __attribute__((always_inline)) {
+#pragma unroll
+      for (int m = 0; m < MB; ++m)
+#pragma unroll
+        for (int n = 0; n < NB16; ++n) acc4[m][n] = floatx4{0.f, 0.f, 0.f, 0.f};
+    };
+    zero4();
+    wait_stages(IC<T::AHEAD - 1>{});  // stage 0 landed
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+      rd_raw(lds, m, 0);
+      rd_raw(lds, m, 1);
+      if (m < MB - 1) {
+#pragma unroll
+        for (int q = 0; q < NSUB; ++q) sub(m, q);
+      }
+    }
+#pragma unroll
+    for (int n = 0; n < NB16; ++n)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) rd_b(lds, n, p);
+    int rb = 1 % T::NBUF;          // ring slot of stage j + 1
+    int ib = T::AHEAD % T::NBUF;   // ring slot stage j + AHEAD goes to (8-wave tiles)
+    for (int j = 0; j < S; ++j) {
+      // stage j + 1 landed.  DEEP: stage j's slot is refilled next, and this wave's reads
+      // of it (previous iteration) must have returned; else the slot refilled is stage
+      // j - 1's, whose fragments have been multiplied.
+      if constexpr (!T::LDR) {
+        wait_stages(IC<T::AHEAD - 2>{});
+      } else {
+        if constexpr (T::DEEP) __builtin_amdgcn_s_waitcnt(0xC07F);
+        asm volatile("s_barrier" ::: "memory");
+      }
+      const unsigned char* st = lds + rb * T::STAGE;
+      static_for<NM16>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        constexpr int m = i / RS, w = i % RS, n = w / 6, term = w % 6;
+        // smallest terms first (gemm_f32.hpp's x6 order): a2b0 a1b1 a0b2 a1b0 a0b1 a0b0
+        constexpr int pa = term == 0 ? 2 : term == 1 || term == 3 ? 1 : 0;
+        constexpr int pb = term == 0 || term >= 3 ? (term == 4 ? 1 : 0) : term == 1 ? 1 : 2;
+        acc4[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, au[m][pa]), bw[n][pb],
+                                                             acc4[m][n], 0, 0, 0);
+        if constexpr (w >= 2 && w < 2 + NSUB) sub((m + MB - 1) % MB, w - 2);
+        if constexpr (w == 2 + NSUB || w == 3 + NSUB) rd_raw(st, m, w - 2 - NSUB);
+        if constexpr (m == MB - 1 && term == 2) rd_b(st, n, 2);
+        if constexpr (m == MB - 1 && term == 4) rd_b(st, n, 1);
+        if constexpr (m == MB - 1 && term == 5) rd_b(st, n, 0);
+        if constexpr (!T::LDR && i % T::DSTEP == 0 && i / T::DSTEP < T::CNT_HI) issue_one(ib, i / T::DSTEP);
+        __builtin_amdgcn_sched_barrier(0);
+      });
+      if constexpr (!T::LDR) {
+        advance();
+        ib = ib + 1 == T::NBUF ? 0 : ib + 1;
+      }
+      rb = rb + 1 == T::NBUF ? 0 : rb + 1;
+      if (++c_st == nst) {
+        c_st = 0;
+        int m0, n0;
+        coords(c_i, m0, n0);
+        store_wave_tile16<EPI, MB, NB16>(acc4, m0 + wm * T::WM, n0 + wn * T::WN, M, N, bias, resid, ldr, out, ldo,
+                                         lane);
+        zero4();
+        ++c_i;
+      }
+    }
+    if constexpr (!T::LDR) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing re-read DMAs
+    return;
+  }
   wait_stages(IC<T::AHEAD - 1>{});  // stage 0 landed
   Frags f0 = {}, f1 = {};
   read_frags(0, 0, f0);
@@ -514,23 +660,31 @@ __global__ __launch_bounds__(256) void split_w3_kernel(const float* __restrict__
   }
 }
 
-// Product tiles (mq_debug_gemm_x6p tile codes 0-3).  Measured at M = 8192 (BERT-base
-// batched shapes, tools/gemm_x6p_bench.py): the loader-wave 128 x 192 tile runs at 0.42-0.50
-// of the 417 TF fp32-equivalent peak, the 8-wave slot-scheduled ones at 0.44-0.50, the
-// first cut (8 waves, DMAs in a burst after the barrier, scheduler's own order) 0.34-0.45.
-using X6p0 = X6pTile<2, 2, 2, 3, 4, 1, 4, true, 0, 1, 0, 6, true>;  // 128 x 192, 4 compute + 4 loader waves
-using X6p1 = X6pTile<4, 1, 2, 3, 4, 1, 4, true, 0, 1, 0, 6, true>;  // 256 x 96, same
-using X6p2 = X6pTile<4, 2, 1, 3, 4, 1, 4, true, 0, 2, 1, 6>;        // 128 x 192, 8 waves, DMAs from 0-3
-using X6p3 = X6pTile<4, 2, 2, 3, 4, 1, 8, true, 0, 6, 1, 8>;        // 256 x 192, 8 waves
-// measurement variants (tile codes 4-6; 7 is a product tile)
-using X6p4 = X6pTile<2, 2, 2, 3, 3, 2, 4, true, 0, 1, 0, 6, true>;  // tile 0 with 32-deep stages, 3 slots
-using X6p5 = X6pTile<2, 2, 2, 3, 4, 1, 4, true, 0, 1, 0, 4, true>;  // tile 0, split from slot 4
-using X6p6 = X6pTile<2, 2, 2, 3, 5, 1, 4, true, 0, 1, 0, 6, true>;  // tile 0 with 5 slots
-using X6p7 = X6pTile<2, 2, 1, 3, 4, 1, 4, true, 0, 1, 0, 6, true>;  // 64 x 192, loaders (product: out-proj)
+// Product tiles (mq_debug_gemm_x6p tile codes 0-3, 7), all on the M16 k-step
+// (v_mfma_f32_16x16x32_bf16, 32-deep stages).  Measured at M = 8192 (BERT-base batched
+// shapes, tools/gemm_x6p_bench.py --ab, profiles/mfma16/gemm_ab.jsonl): the loader-wave
+// 128 x 192 tile runs QKV / out-proj / FFN-up / FFN-down at 240 / 207 / 221 / 251 TF
+// fp32-equivalent (215 / 180 / 203 / 217 on the 32x32x16 k-step, tile 16, same process).
+using X6p0 = X6pTile<2, 2, 2, 3, 3, 2, 4, true, 0, 1, 0, 6, true, true>;         // 128 x 192, 4 compute + 4 loader waves
+using X6p1 = X6pTile<4, 1, 2, 3, 3, 2, 4, true, 0, 1, 0, 6, true, true>;         // 256 x 96, same
+using X6p2 = X6pTile<4, 2, 1, 3, 3, 2, 4, true, 0, 2, 1, 6, false, true>;        // 128 x 192, 8 waves, DMAs from 0-3
+using X6p3 = X6pTile<4, 2, 2, 3, 2, 2, 8, true, 0, 6, 1, 8, false, true, true>;  // 256 x 192, 8 waves, 2 slots
+// measurement variants (tile codes 4-6; 7 is a product tile): the ring 3 stages ahead
+using X6p4 = X6pTile<2, 2, 2, 3, 3, 2, 4, true, 0, 1, 0, 6, true, true, true>;   // tile 0
+using X6p5 = X6pTile<2, 2, 1, 3, 3, 2, 4, true, 0, 1, 0, 6, true, true, true>;   // tile 7
+using X6p6 = X6pTile<4, 1, 2, 3, 3, 2, 4, true, 0, 1, 0, 6, true, true, true>;   // tile 1
+using X6p7 = X6pTile<2, 2, 1, 3, 3, 2, 4, true, 0, 1, 0, 6, true, true>;         // 64 x 192, loaders
+// tile codes 16 / 17: the former k-step of tiles 0 / 7 (v_mfma_f32_32x32x16_bf16, 16-deep
+// stages, 4 slots), kept to re-measure the two MFMA shapes in one library.  Same split and
+// products in the same order but 16 k per MFMA: fp32-class, NOT bit-identical to the others.
+using X6p16 = X6pTile<2, 2, 2, 3, 4, 1, 4, true, 0, 1, 0, 6, true>;
+using X6p17 = X6pTile<2, 2, 1, 3, 4, 1, 4, true, 0, 1, 0, 6, true>;
 
 template <class T, int EPI>
 void launch_t(const X6pArgs& g, int num_cus, hipStream_t s) {
-  if (g.K % (16 * T::KS) != 0) {  // stage depth must divide K: the 16-deep default tile
+  // stage depth must divide K: else the 16-deep 8-wave tile (32x32x16 arithmetic).  No caller
+  // gets here: launch_gemm's K is a multiple of kBK = 32, as mq_debug_gemm_x6p's.
+  if (g.K % (16 * T::KS) != 0) {
     launch_t<X6pTile<4, 2, 1, 3, 4>, EPI>(g, num_cus, s);
     return;
   }
@@ -568,6 +722,8 @@ void launch_tile(const X6pArgs& g, int tile, int num_cus, hipStream_t s) {
     case 5: launch_t<X6p5, EPI>(g, num_cus, s); return;
     case 6: launch_t<X6p6, EPI>(g, num_cus, s); return;
     case 7: launch_t<X6p7, EPI>(g, num_cus, s); return;
+    case 16: launch_t<X6p16, EPI>(g, num_cus, s); return;
+    case 17: launch_t<X6p17, EPI>(g, num_cus, s); return;
     default: launch_t<X6p0, EPI>(g, num_cus, s); return;
   }
 }
@@ -593,13 +749,10 @@ int x6p_pick_tile(int M, int N, int num_cus) {
 
 void launch_gemm_x6p(const X6pArgs& g, int epi, int tile, int num_cus, hipStream_t s) {
   if (tile < 0) {
+    // (out-proj, N = K = 768 at M = 8192, ran 64 x 192 tiles two per CU on the 32x32x16
+    // k-step; on the 16x16x32 one 128 x 192 is the faster there too: 46.8 vs 50.0 / 51.6 us,
+    // profiles/mfma16/gemm_ab.jsonl)
     tile = x6p_pick_tile(g.M, g.N, num_cus);
-    // a short, narrow GEMM (out-proj: N = K = 768) that 128 x 192 covers in one round of
-    // one tile per CU runs 64 x 192 tiles, two per CU: the ring carries into the second
-    // tile, the first's epilogue overlaps its loads (57.2 vs 59.3 us at M = 8192; slower
-    // on the deeper and wider shapes, tools/gemm_x6p_bench.py)
-    const int64_t t0 = (int64_t)((g.M + 127) / 128) * ((g.N + 191) / 192);
-    if (g.K <= 768 && g.N <= 768 && t0 <= num_cus && t0 * 2 > num_cus) tile = 7;
   }
   switch (epi) {
     case EPI_GELU_ERF: launch_tile<EPI_GELU_ERF>(g, tile, num_cus, s); return;
@@ -636,7 +789,7 @@ int mq_debug_gemm_x6p(const float* A, const void* W3, const float* bias, const f
   // plain walk); below 100 the automatic pick
   const int rx = tile >= 100 ? tile / 100 - 1 : -1;
   if (tile >= 100) tile %= 100;
-  MQ_CHECK_ARG(epi >= 0 && epi <= 3 && tile >= -1 && tile <= 15 && rx <= 8, "bad epi/tile");
+  MQ_CHECK_ARG(epi >= 0 && epi <= 3 && tile >= -1 && tile <= 17 && rx <= 8, "bad epi/tile");
   int dev = 0, cus = 256;
   (void)hipGetDevice(&dev);
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);

@@ -1,7 +1,8 @@
 // gemm_x6p.hpp - host interface of the pre-split split-f32 GEMM (gemm_x6p.hip).
 //
 // The split-f32 ("x6") arithmetic of gemm_f32.hpp - every fp32 operand split exactly into
-// three bf16 planes, six v_mfma_f32_32x32x16_bf16 per product, fp32 accumulation - with
+// three bf16 planes, six bf16 MFMAs per product (v_mfma_f32_16x16x32_bf16: 32 k per
+// MFMA on 16x16 blocks, gemm_f32.hpp's M16 tiles), fp32 accumulation - with
 // the weight operand split ONCE, when the weights are loaded, into a fragment-blocked
 // plane image ("W3"):
 //
@@ -90,9 +91,9 @@ struct X6pArgs {
 // Tile shapes (workgroups of 8 waves, one per CU): 0 = 128 x 192 (4 compute + 4 loader
 // waves; the default: M = 8192 at N = 768 / 1536 / 2304 / 3072 gives whole rounds of 256
 // tiles), 1 = 256 x 96 (same waves), 2 = 128 x 192 and 3 = 256 x 192 (8 compute waves),
-// 7 = 64 x 192 (4 + 4 waves; out-proj-like shapes, see launch_gemm_x6p); 4-6 are
-// measurement variants of tile 0.  -1 = the pick below (+ tile 7 for N, K <= 768 when
-// 128 x 192 would run a single round).
+// 7 = 64 x 192 (4 + 4 waves); 4-6 are tiles 0 / 7 / 1 with the ring one stage further
+// ahead (measurement); 16 / 17 are tiles 0 / 7 on the former 32x32x16 k-step (measurement;
+// fp32-class, not bit-identical to the others).  -1 = the pick below.
 int x6p_pick_tile(int M, int N, int num_cus);
 // epi: EPI_BIAS / EPI_GELU_ERF / EPI_GELU_TANH / EPI_RESID (gemm_epi.hpp)
 void launch_gemm_x6p(const X6pArgs& g, int epi, int tile, int num_cus, hipStream_t s);

@@ -38,8 +38,64 @@ def timed(fn, iters):
     return sorted(runs)[len(runs) // 2]
 
 
+def ab(a, dev, st):
+    """--ab OLD:NEW[,OLD:NEW...]: per shape, time the two K2p tile codes of each pair in one
+    process, alternating (old, new, old, new, ...) `--reps` times on the same random
+    operands; one JSON line per (shape, pair) with every round's us per launch."""
+    pairs = [tuple(int(t) for t in p.split(":")) for p in a.ab.split(",")]
+    out_f = open(a.out, "a") if a.out else None
+    for name in a.shapes.split(","):
+        M, N, K, epi = SHAPES[name]
+        g = torch.Generator(device=dev).manual_seed(1)
+        A = torch.randn(M, K, device=dev, generator=g)
+        W = torch.randn(N, K, device=dev, generator=g) * 0.05
+        b = torch.randn(N, device=dev, generator=g)
+        R = torch.randn(M, N, device=dev, generator=g)
+        out = torch.empty(M, N, device=dev)
+        w3 = torch.empty(_lib.lib().mq_debug_w3_bytes(N, K), dtype=torch.uint8, device=dev)
+        _lib.call("mq_debug_split_w3", _lib.ptr(W), N, K, _lib.ptr(w3), st)
+        ref = A.double() @ W.double().T + b.double() if a.check else None
+
+        def run(t):
+            _lib.call("mq_debug_gemm_x6p", _lib.ptr(A), _lib.ptr(w3), _lib.ptr(b), _lib.ptr(R), _lib.ptr(out),
+                      M, N, K, 0 if a.check else epi, t, st)
+
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for old, new in pairs:
+            rounds = {old: [], new: []}
+            err = {}
+            for t in (old, new):
+                for _ in range(3):
+                    run(t)
+                if ref is not None:
+                    torch.cuda.synchronize()
+                    err[t] = float((out.double() - ref).abs().max())
+            for _ in range(a.reps):
+                for t in (old, new):
+                    e0.record()
+                    for _ in range(a.iters):
+                        run(t)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    rounds[t].append(round(e0.elapsed_time(e1) * 1000.0 / a.iters, 2))
+            med = {t: sorted(v)[len(v) // 2] for t, v in rounds.items()}
+            line = json.dumps({"shape": name, "M": M, "N": N, "K": K, "old_tile": old, "new_tile": new,
+                               "old_us": rounds[old], "new_us": rounds[new], "old_med": med[old],
+                               "new_med": med[new], "old_over_new": round(med[old] / med[new], 4),
+                               "old_tflops": round(2.0 * M * N * K / med[old] / 1e6, 1),
+                               "new_tflops": round(2.0 * M * N * K / med[new] / 1e6, 1),
+                               "max_abs_err_f64": err or None})
+            print(line, flush=True)
+            if out_f:
+                out_f.write(line + "\n")
+                out_f.flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ab", default="", help="OLD:NEW tile code pairs to time alternating (see ab())")
+    ap.add_argument("--out", default="", help="--ab: also append the JSON lines to this file")
+    ap.add_argument("--check", action="store_true", help="--ab: bias epilogue, report max |err| vs float64")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--f32-tiles", default="0,1,5,6,7")
@@ -50,6 +106,9 @@ def main():
     REPS = a.reps
     dev = torch.device("cuda", 0)
     st = _lib.stream_handle()
+    if a.ab:
+        ab(a, dev, st)
+        return
     for name in a.shapes.split(","):
         M, N, K, epi = SHAPES[name]
         g = torch.Generator(device=dev).manual_seed(1)
