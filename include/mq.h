@@ -292,6 +292,14 @@ int mq_encoder_set_graphs(mq_encoder* enc, int enabled);
  *                                fused attention's two head groups add into ONE output plane
  *                                (two addends per element: bitwise the sum the consumer took), so
  *                                the next QKV / FFN-up reads one plane of rows; 1 = two planes.
+ *   MQ_ENC_OPT_LN_FOLD           split-f32 precision, batched forward, hidden 768, every full-M
+ *                                GEMM on the split-f32 tiles (ceil(M / 128) * (hidden / 192) >=
+ *                                CUs): 1 = the LayerNorms folded into the GEMMs - out-proj /
+ *                                FFN-down write the raw sums and per-row partials, FFN-up / the
+ *                                next QKV multiply them by gamma-scaled weights and apply mean /
+ *                                rstd in their epilogue (no LayerNorm launch on the full-M
+ *                                layers); 0 = a LayerNorm launch each.  Shapes outside the gate
+ *                                run as with 0, bit for bit.
  * Setting an option drops the handle's captured graphs. */
 #define MQ_ENC_OPT_ROWS_MAX 0
 #define MQ_ENC_OPT_ROWS_SPLITS 1
@@ -304,6 +312,7 @@ int mq_encoder_set_graphs(mq_encoder* enc, int enabled);
 #define MQ_ENC_OPT_RESIDENT_LAYERS 8
 #define MQ_ENC_OPT_X6_PRESPLIT 9
 #define MQ_ENC_OPT_ROWS_PLANES 10
+#define MQ_ENC_OPT_LN_FOLD 11
 int mq_encoder_set_option(mq_encoder* enc, int option, int value);
 int mq_encoder_get_option(const mq_encoder* enc, int option, int* value);
 int mq_encoder_set_timing(mq_encoder* enc, int enabled);
@@ -359,6 +368,19 @@ int mq_debug_split_w3(const float* W, int N, int K, void* w3, void* stream);
  * Asynchronous on `stream`.  K % 32 == 0. */
 int mq_debug_gemm_x6p(const float* A, const void* W3, const float* bias, const float* resid,
                       float* out, int M, int N, int K, int epi, int tile, void* stream);
+/* One K2p launch with a LayerNorm-fold epilogue (tile 0, 1 or -1 = the pick; no fill-the-chip
+ * gate).  epi 5 = the producer: out = acc + bias + LN(resid) with the residual normalised from
+ * stats_in [M][8] (mean, M2) pairs and g / b [N] (stats_in NULL: the residual as it is), and
+ * the partials of out written to stats_out [M][8]; N = 768.  epi 6 / 7 / 8 = the consumers
+ * (bias / GELU erf / GELU tanh): out = epi(rho_r (acc - mu_r s_fold[n]) + bias[n]), (mu, rho)
+ * from stats_in and eps; K = 768.  mq_debug_ln_fold_weight builds Wg = g W (whose W3 image the
+ * consumer multiplies), s and c (the consumer's bias) from W [N][K], bias, g, b. */
+int mq_debug_gemm_x6p_ln(const float* A, const void* W3, const float* bias, const float* resid,
+                         float* out, int M, int N, int K, int epi, int tile, const float* stats_in,
+                         float* stats_out, const float* g, const float* b, const float* s_fold,
+                         float eps, void* stream);
+int mq_debug_ln_fold_weight(const float* W, const float* bias, const float* g, const float* b, int N,
+                            int K, float* Wg, float* s_out, float* c_out, void* stream);
 
 /* The int8 screen (K9q) alone for one host query: its kc candidates (screen scores
  * desc, ids; slots past the survivors hold (tau, -1)) and the int8 shadow's statistics

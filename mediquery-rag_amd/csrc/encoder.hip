@@ -39,8 +39,8 @@ namespace mq {
 // gamma + beta; the tiles of column 0 also store LN(y) to x, the residual input of the
 // following residual GEMM.  No LayerNorm launch and no y -> x round trip.  Two-pass-class
 // statistics in fp32; ln_kernel's summation order differs (results agree to rounding).
-constexpr int kLnPartW = 96;   // columns per partial: the producer's wave tile (F32Tile<4,1,1,3>)
-constexpr int kLnMaxParts = 8;  // partials per row: the path runs at H = 768 (BERT-base)
+// (kLnPartW = 96 columns per partial, the producer's wave tile F32Tile<4,1,1,3>, and
+// kLnMaxParts = 8 partials per row - the path runs at H = 768 - are gemm_x6p.hpp's.)
 struct LnArgs {
   float* stats_out;       // producer: [M][nt] (mean, M2) pairs
   const float* stats_in;  // consumer: the producer's pairs for A's rows
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(T::THREADS, T::WG_PER_CU) void gemm_nt_kernel(const
                                                          const float* __restrict__ bias,
                                                          const float* __restrict__ resid, int ldr,
                                                          float* __restrict__ out, int ldo, int M,
-                                                         int N, int K, LnArgs ln, int rx) {
+                                                         int N, int K, LnArgs ln, int rx, LnFold lf) {
   __shared__ __attribute__((aligned(16))) float lds[2 * T::STAGE_FLOATS];
   __shared__ float2 ln_st[LN_IN ? 2 * T::BM : 1];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -215,9 +215,10 @@ __global__ __launch_bounds__(T::THREADS, T::WG_PER_CU) void gemm_nt_kernel(const
 #pragma unroll
           for (int e = 0; e < 4; ++e) a4[m][n][e] = acc[m >> 1][n >> 1][4 * (2 * (m & 1) + (n & 1)) + e];
       store_wave_tile16<EPI, 2 * T::TM, 2 * T::TN>(a4, m0 + wm * T::WM, n0 + wn * T::WN, M, N, bias, resid, ldr, out,
-                                                   ldo, lane);
+                                                   ldo, lane, lf);
       return;
     }
+    static_assert(T::M16 || EPI < EPI_RESID_LN_STATS, "the LayerNorm-fold epilogues are on the 16x16 store");
     if constexpr (EPI == EPI_RESID_STATS) {
       // y = acc + bias + resid, then per row the partial (mean, M2) of y over the wave
       // tile's WN = kLnPartW columns: the 32 lanes of a lane half hold a row's columns
@@ -1097,6 +1098,23 @@ __global__ __launch_bounds__(256) void ln_kernel(const float* __restrict__ src, 
   }
 }
 
+// LayerNorm of `rows` rows `stride` floats apart, in place (a wave holds its whole row before
+// it writes): the B CLS rows of the raw y that the CLS-only last layer reads normalised when
+// the LayerNorms are folded into the GEMMs.  ln_kernel's per-row arithmetic.
+template <int VPL>
+__global__ __launch_bounds__(256) void ln_rows_inplace_kernel(float* x, int rows, int64_t stride,
+                                                              const float* __restrict__ g,
+                                                              const float* __restrict__ b, float eps) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  float* xr = x + (int64_t)row * stride;
+  floatx4 v[VPL];
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) v[i] = *reinterpret_cast<const floatx4*>(xr + (i * 64 + lane) * 4);
+  ln_row_store<VPL>(v, g, b, eps, xr, lane);
+}
+
 // ------------------------------------------------------------ K3 attention ----
 // One 64-thread workgroup (one wave) per (sequence, head, 32-query tile); dh = 64.
 // Scores are computed TRANSPOSED on the f32 MFMA: S^T[key][query] = K . Q^T, so keys
@@ -1720,6 +1738,12 @@ struct LayerW {
   const unsigned char *wqkv3 = nullptr, *wo3 = nullptr, *w13 = nullptr, *w23 = nullptr;
   // frag16 images of the same four (the few-row kernels' weight operands)
   const float *wqkvf = nullptr, *wof = nullptr, *w1f = nullptr, *w2f = nullptr;
+  // LayerNorm fold (build_fold): w1 scaled by this layer's ln1 gamma and wqkv by the PREVIOUS
+  // layer's ln2 gamma (layers >= 1) as W3 images (x6_presplit) or fp32 (the re-split tiles),
+  // and the fold's s / c vectors
+  const unsigned char *w1g3 = nullptr, *wqkvg3 = nullptr;
+  const float *w1gf = nullptr, *wqkvgf = nullptr;
+  const float *w1s = nullptr, *w1c = nullptr, *wqkvs = nullptr, *wqkvc = nullptr;
 };
 
 int64_t weight_count(const mq_bert_config& c) {
@@ -1747,6 +1771,7 @@ struct GemmArgs {
   int M, N, K;
   int nt = 0;  // few-row split-K launches: weights load non-temporally (layers past resident_layers)
   const void* W3 = nullptr;  // split-f32: W's W3 plane image (K2p, gemm_x6p.hip)
+  LnFold lf{};               // the LayerNorm-fold epilogues (launch_gemm_fold)
 };
 
 template <class T, int EPI, bool LN_IN = false>
@@ -1757,7 +1782,7 @@ void launch_gemm_t(const GemmArgs& g, int num_cus, hipStream_t s, const LnArgs& 
   const int tiles_m = (g.M + T::BM - 1) / T::BM, tiles_n = (g.N + T::BN - 1) / T::BN;
   const int rx = region_pick_rx(tiles_m, tiles_n, (double)T::BM * g.K * 4, (double)T::BN * g.K * 4, grid);
   hipLaunchKernelGGL((gemm_nt_kernel<T, EPI, LN_IN>), dim3(grid), dim3(T::THREADS), 0, s, g.A, g.lda, g.W,
-                     g.bias, g.resid, g.ldr, g.out, g.ldo, g.M, g.N, g.K, ln, rx);
+                     g.bias, g.resid, g.ldr, g.out, g.ldo, g.M, g.N, g.K, ln, rx, g.lf);
 }
 
 using GemmBig = F32Tile<2, 2, 2, 2>;    // 128 x 128
@@ -1834,6 +1859,47 @@ void launch_splitk(const GemmArgs& g, int S, hipStream_t s) {
                      s, g.slab, S, g.M, g.N, g.bias, g.resid, g.ldr, g.out, g.ldo);
 }
 
+// the split-f32 tile (0 / 1 / 2 = 128 x 128 / 96 / 64) that wastes the least of its last round
+int x6_tile_pick(const GemmArgs& g, int num_cus) {
+  const int bns[3] = {128, 96, 64};
+  const double effs[3] = {1.0, 0.96, 0.9};
+  const int64_t slots = 2 * (int64_t)num_cus;
+  int best = 0;
+  double best_cost = 1e300;
+  for (int i = 0; i < 3; ++i) {
+    const int64_t tiles = (int64_t)((g.M + 127) / 128) * ((g.N + bns[i] - 1) / bns[i]);
+    const double cost = (double)((tiles + slots - 1) / slots) * 128 * bns[i] / effs[i];
+    if (cost < best_cost) {
+      best_cost = cost;
+      best = i;
+    }
+  }
+  return best;
+}
+
+// A split-f32 GEMM with a LayerNorm-fold epilogue (g.lf; forward_vpl's gate has checked that
+// it fills the chip).  K2p on the W3 image when there is one; else the split-f32 tiles that
+// re-split both operands - the producer pinned to the 128 x 96 tile, whose wave tile is the
+// partial width - with the same epilogue code on the same accumulators: the same bits.
+template <int EPI>
+void launch_gemm_fold(const GemmArgs& g, int num_cus, hipStream_t s) {
+  if (g.W3) {
+    X6pArgs a{g.A, g.lda, g.W3, g.bias, g.resid, g.ldr, g.out, g.ldo, g.M, g.N, g.K};
+    a.lf = g.lf;
+    launch_gemm_x6p(a, EPI, -1, num_cus, s);
+    return;
+  }
+  if constexpr (EPI == EPI_RESID_LN_STATS) {
+    launch_gemm_t<X6T96, EPI>(g, num_cus, s);
+  } else {
+    switch (x6_tile_pick(g, num_cus)) {
+      case 0: launch_gemm_t<X6Big, EPI>(g, num_cus, s); return;
+      case 1: launch_gemm_t<X6T96, EPI>(g, num_cus, s); return;
+      default: launch_gemm_t<X6Mid, EPI>(g, num_cus, s); return;
+    }
+  }
+}
+
 template <int EPI>
 void launch_gemm(const GemmArgs& g, int num_cus, hipStream_t s, bool x6 = false, int splitk_cap = 16,
                  int splitk_tiles = 0) {
@@ -1853,20 +1919,7 @@ void launch_gemm(const GemmArgs& g, int num_cus, hipStream_t s, bool x6 = false,
     return;
   }
   if (x6) {  // split-f32 tiles (both operands split while staged): same waste model over 128x{128,96,64}
-    const int bns[3] = {128, 96, 64};
-    const double effs[3] = {1.0, 0.96, 0.9};
-    const int64_t slots = 2 * (int64_t)num_cus;
-    int best = 0;
-    double best_cost = 1e300;
-    for (int i = 0; i < 3; ++i) {
-      const int64_t tiles = (int64_t)((g.M + 127) / 128) * ((g.N + bns[i] - 1) / bns[i]);
-      const double cost = (double)((tiles + slots - 1) / slots) * 128 * bns[i] / effs[i];
-      if (cost < best_cost) {
-        best_cost = cost;
-        best = i;
-      }
-    }
-    launch_gemm_tile<EPI>(g, 5 + best, num_cus, s);
+    launch_gemm_tile<EPI>(g, 5 + x6_tile_pick(g, num_cus), num_cus, s);
     return;
   }
   struct Cand {
@@ -1908,6 +1961,12 @@ void launch_gemm_ln_in(const GemmArgs& g, const LnArgs& ln, int num_cus, hipStre
   else
     launch_gemm_t<GemmT96, EPI, true>(g, num_cus, s, ln);
 }
+
+// MQ_ENC_OPT_LN_FOLD's default (DESIGN.md section 4 has the A/B that decides it)
+#ifndef MQ_LN_FOLD_DEFAULT
+#define MQ_LN_FOLD_DEFAULT 1
+#endif
+constexpr bool kLnFoldDefault = MQ_LN_FOLD_DEFAULT != 0;
 
 // Stage labels for the optional per-kernel-class event timeline.
 enum Stage { ST_EMBED = 0, ST_QKV, ST_ATTN, ST_OPROJ, ST_LN, ST_FFN_UP, ST_FFN_DOWN, ST_POOL, ST_N };
@@ -1957,6 +2016,8 @@ struct mq_encoder {
                                 // measured slower: the consumers' staging VALU)
   Buf lnst;                     // its per-row partials, two sets of [M][H / kLnPartW] (mean, M2)
   bool x6_presplit = true;      // split-f32 batched GEMMs on the W3 images (K2p)
+  bool ln_fold = kLnFoldDefault;  // split-f32 batched forward: LayerNorm folded into the GEMMs (LnFold)
+  Buf wfold3, wfoldf, sfold;    // its gamma-scaled weights (W3 images / fp32) and s, c vectors
   bool rows_planes = false;     // few-row forward: keep the two-plane hand-offs (no FL_ACC merge)
   bool use_graphs = false;  // eager measured faster for one query (0.628 vs 0.645 ms: the
                             // graph path stages ids / mask / out through its own buffers)
@@ -1993,6 +2054,64 @@ int build_w3(mq_encoder* e) {
   }
   MQ_HIP(hipGetLastError());
   MQ_HIP(hipStreamSynchronize(nullptr));
+  return MQ_OK;
+}
+
+// LayerNorm fold (MQ_ENC_OPT_LN_FOLD): Wg = gamma W for every layer's w1 (ln1) and, from layer
+// 1 on, wqkv (the previous layer's ln2), with s[n] = sum_k Wg[n,k] and c[n] = b[n] + sum_k
+// beta_k W[n,k] - as W3 images for K2p (x6_presplit; 287 MB for BERT-base beside the 510 MB
+// of W3) or as fp32 for the re-split tiles (191 MB), whichever the current mode needs and
+// does not have yet.  The unfolded weights stay: layer 0 and every shape outside the gate use
+// them.  Synchronous; a no-op unless the option is on, the precision split-f32, H = 768.
+int build_fold(mq_encoder* e) {
+  const mq_bert_config& c = e->cfg;
+  const int H = c.hidden, F = c.ffn;
+  if (!e->ln_fold || e->precision != MQ_DTYPE_F32X6 || !e->loaded || e->layers.empty() ||
+      H != kLnPartW * kLnMaxParts || F % 32 != 0)
+    return MQ_OK;
+  const bool img = e->x6_presplit;
+  if (img ? e->layers[0].w1g3 != nullptr : e->layers[0].w1gf != nullptr) return MQ_OK;
+  const size_t nl = e->layers.size();
+  DeviceGuard dg(e->device);
+  int rc = e->sfold.ensure(nl * 2 * ((size_t)F + 3 * H));
+  if (rc) return rc;
+  Buf tmp;  // one weight's fp32 Wg, the split's source
+  if (img) {
+    rc = e->wfold3.ensure((nl * w3_bytes(F, H) + (nl - 1) * w3_bytes(3 * H, H) + 3) / 4);
+    if (!rc) rc = tmp.ensure((size_t)std::max(F, 3 * H) * H);
+  } else {
+    rc = e->wfoldf.ensure((nl * (size_t)F + (nl - 1) * (size_t)3 * H) * H);
+  }
+  if (rc) return rc;
+  unsigned char* p3 = reinterpret_cast<unsigned char*>(e->wfold3.p);
+  float* pf = e->wfoldf.p;
+  float* ps = e->sfold.p;
+  const LayerW* prev = nullptr;
+  for (LayerW& w : e->layers) {
+    auto one = [&](const float* W, const float* bias, const float* g, const float* b, int n, const unsigned char*& d3,
+                   const float*& df, const float*& ds, const float*& dc) {
+      float* wg = img ? tmp.p : pf;
+      launch_ln_fold_weight(W, bias, g, b, n, H, wg, ps, ps + n, nullptr);
+      ds = ps;
+      dc = ps + n;
+      ps += 2 * n;
+      if (img) {
+        launch_split_w3(wg, n, H, p3, nullptr);
+        d3 = p3;
+        p3 += w3_bytes(n, H);
+      } else {
+        df = pf;
+        pf += (size_t)n * H;
+      }
+    };
+    one(w.w1, w.b1, w.ln1g, w.ln1b, F, w.w1g3, w.w1gf, w.w1s, w.w1c);
+    if (prev) one(w.wqkv, w.bqkv, prev->ln2g, prev->ln2b, 3 * H, w.wqkvg3, w.wqkvgf, w.wqkvs, w.wqkvc);
+    prev = &w;
+  }
+  const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(nullptr);
+  tmp.release();
+  MQ_HIP(e1);
+  MQ_HIP(e2);
   return MQ_OK;
 }
 
@@ -2101,6 +2220,23 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* mask, int B, int L, fl
   float* st2 = lnl ? e->lnst.p + (size_t)2 * M * nt : nullptr;  // FFN-down -> next QKV
   bool y_pending = false;  // x holds LN2's input y (+ st2) instead of the LayerNorm output
   const LayerW* prev = nullptr;
+  // LayerNorm folded into the split-f32 GEMMs (LnFold) on the full-M layers: every one of
+  // their GEMMs on the split-f32 tiles (launch_gemm's fill-the-chip test at the narrowest, N
+  // = H), the folded weights built.  x and y are then the two raw-y buffers: out-proj writes
+  // y (+ st1), FFN-down x (+ st2), each reading the other as its residual.
+  const LayerW w0 = e->layers.empty() ? LayerW{} : e->layers[0];
+  const bool fold = e->ln_fold && e->precision == MQ_DTYPE_F32X6 && M > 256 && H == kLnPartW * kLnMaxParts &&
+                    F % 32 == 0 && (int64_t)((M + 127) / 128) * ((H + 191) / 192) >= e->num_cus &&
+                    e->lnst.n >= (size_t)4 * M * nt && (e->x6_presplit ? w0.w1g3 != nullptr : w0.w1gf != nullptr);
+  float* fst1 = e->lnst.p;
+  float* fst2 = e->lnst.p + (size_t)2 * M * nt;
+  bool raw = false;  // fold: x holds the previous layer's raw FFN-down sum (+ fst2), not LN2 of it
+  auto fold_gemm = [&](auto epi, GemmArgs g, int stage) {
+    e->tl.mark(s, stage);
+    if (!e->x6_presplit) g.W3 = nullptr;
+    g.lf.eps = c.ln_eps;
+    launch_gemm_fold<decltype(epi)::value>(g, e->num_cus, s);
+  };
   auto ln_args = [&](const float* stats, const float* g, const float* b) {
     LnArgs a{};
     a.stats_in = stats;
@@ -2130,9 +2266,22 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* mask, int B, int L, fl
     // few rows (single queries past the few-row limit): the layers past resident_layers
     // stream their weights non-temporally in the split-K GEMMs (as forward_rows does)
     const int lnt = M <= 256 && (int)li >= e->resident_layers ? 1 : 0;
+    // the CLS-only tail (the B CLS rows past attention) runs unfolded
+    const bool fold_layer = fold && !(cls_only && L > 1);
+    // the folded QKV weights' rows [row0, ..): LN2 of the previous layer applied in the epilogue
+    auto qkv_fold = [&](GemmArgs g, int row0) {
+      g.W = w.wqkvgf ? w.wqkvgf + (int64_t)row0 * H : nullptr;
+      g.W3 = w.wqkvg3 ? w.wqkvg3 + w3_row_offset(row0, H) : nullptr;
+      g.bias = w.wqkvc + row0;
+      g.lf.s = w.wqkvs + row0;
+      g.lf.stats_in = fst2;
+      fold_gemm(IC<EPI_BIAS_LNFOLD>{}, g, ST_QKV);
+    };
     auto qkv_gemm = [&](GemmArgs g) {
       g.nt = lnt;
-      if (y_pending) {
+      if (raw) {
+        qkv_fold(g, (int)(g.W - w.wqkv) / H);
+      } else if (y_pending) {
         e->tl.mark(s, ST_QKV);
         launch_gemm_ln_in<EPI_BIAS>(g, ln_args(st2, prev->ln2g, prev->ln2b), e->num_cus, s);
       } else {
@@ -2146,6 +2295,11 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* mask, int B, int L, fl
                   3 * H, M, 2 * H, H};
       if (w.wqkv3) kv.W3 = w.wqkv3 + w3_row_offset(H, H);
       qkv_gemm(kv);
+      if (raw) {  // the CLS rows of the raw y, normalised in place for the Q GEMM and the tail
+        e->tl.mark(s, ST_LN);
+        hipLaunchKernelGGL((ln_rows_inplace_kernel<VPL>), dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, e->x.p, B,
+                           (int64_t)L * H, prev->ln2g, prev->ln2b, c.ln_eps);
+      }
       GemmArgs q{e->slab.p, e->slab.n, e->x.p, L * H, w.wqkv, w.bqkv, nullptr, 0, e->qkv.p, L * 3 * H, B, H, H, lnt};
       q.W3 = w.wqkv3;
       gemm<EPI_BIAS>(e, q, ST_QKV, s);
@@ -2155,6 +2309,8 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* mask, int B, int L, fl
       qkv_gemm(qkv);
     }
     y_pending = false;
+    const bool resid_raw = raw && fold_layer;  // (the tail's residual rows were normalised above)
+    raw = false;
     e->tl.mark(s, ST_ATTN);
     const int qt = cls_only ? 1 : q_tiles;
     launch_attention(B, L, c.heads, qt, H, scale, e->qkv.p, mask, e->ctx.p, s);
@@ -2162,7 +2318,15 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* mask, int B, int L, fl
     // x = LN1(x + ctx Wo^T + bo)  (compact [rows, H], through y) - or, deferred, y + partials
     GemmArgs oproj{e->slab.p, e->slab.n, e->ctx.p, stride, w.wo, w.bo, e->x.p, stride, e->y.p, H, rows, H, H, lnt};
     oproj.W3 = w.wo3;
-    if (lnl_layer) {
+    if (fold_layer) {  // y = ctx Wo^T + bo + (LN2_prev(x) or x), raw, + its partials
+      oproj.lf.stats_out = fst1;
+      if (resid_raw) {
+        oproj.lf.stats_in = fst2;
+        oproj.lf.g = prev->ln2g;
+        oproj.lf.b = prev->ln2b;
+      }
+      fold_gemm(IC<EPI_RESID_LN_STATS>{}, oproj, ST_OPROJ);
+    } else if (lnl_layer) {
       e->tl.mark(s, ST_OPROJ);
       launch_gemm_stats(oproj, stats_out(st1), e->num_cus, s);
     } else {
@@ -2171,7 +2335,18 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* mask, int B, int L, fl
     GemmArgs up{e->slab.p, e->slab.n, lnl_layer ? e->y.p : e->x.p, H, w.w1, w.b1, nullptr, 0, e->ffn.p, F,
                 rows, F, H, lnt};
     up.W3 = w.w13;
-    if (lnl_layer) {  // FFN-up normalises y (LN1) while staging; its column-0 tiles write x
+    if (fold_layer) {  // FFN-up on the raw y with LN1 folded in
+      up.A = e->y.p;
+      up.W = w.w1gf;
+      up.W3 = w.w1g3;
+      up.bias = w.w1c;
+      up.lf.s = w.w1s;
+      up.lf.stats_in = fst1;
+      if (c.gelu == MQ_GELU_TANH)
+        fold_gemm(IC<EPI_GELU_TANH_LNFOLD>{}, up, ST_FFN_UP);
+      else
+        fold_gemm(IC<EPI_GELU_ERF_LNFOLD>{}, up, ST_FFN_UP);
+    } else if (lnl_layer) {  // FFN-up normalises y (LN1) while staging; its column-0 tiles write x
       e->tl.mark(s, ST_FFN_UP);
       if (c.gelu == MQ_GELU_TANH)
         launch_gemm_ln_in<EPI_GELU_TANH>(up, ln_args(st1, w.ln1g, w.ln1b), e->num_cus, s);
@@ -2184,7 +2359,23 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* mask, int B, int L, fl
     }
     GemmArgs down{e->slab.p, e->slab.n, e->ffn.p, F, w.w2, w.b2, e->x.p, H, e->y.p, H, rows, H, F, lnt};
     down.W3 = w.w23;
-    if (lnl_layer && li + 1 < e->layers.size()) {  // LN2 deferred into the next layer's QKV
+    if (fold_layer) {  // x = ffn W2^T + b2 + LN1(y), raw, + its partials: LN2 is the next QKV's
+      const bool last = li + 1 == e->layers.size();
+      down.resid = e->y.p;
+      down.lf.stats_in = fst1;
+      down.lf.g = w.ln1g;
+      down.lf.b = w.ln1b;
+      down.lf.stats_out = fst2;
+      down.out = last ? e->ctx.p : e->x.p;  // (last: the final LayerNorm stays a launch, ctx -> x)
+      fold_gemm(IC<EPI_RESID_LN_STATS>{}, down, ST_FFN_DOWN);
+      if (last) {
+        e->tl.mark(s, ST_LN);
+        hipLaunchKernelGGL((ln_kernel<VPL, 4>), dim3((unsigned)((M + 15) / 16)), dim3(256), 0, s, e->ctx.p, M, w.ln2g,
+                           w.ln2b, c.ln_eps, e->x.p);
+      } else {
+        raw = true;
+      }
+    } else if (lnl_layer && li + 1 < e->layers.size()) {  // LN2 deferred into the next layer's QKV
       e->tl.mark(s, ST_FFN_DOWN);
       launch_gemm_stats(down, stats_out(st2), e->num_cus, s);
       y_pending = true;
@@ -2754,6 +2945,10 @@ int mq_encoder_set_option(mq_encoder* e, int option, int value) {
       MQ_CHECK_ARG(value == 0 || value == 1, "rows_planes must be 0 or 1 (got %d)", value);
       e->rows_planes = value != 0;
       break;
+    case MQ_ENC_OPT_LN_FOLD:
+      MQ_CHECK_ARG(value == 0 || value == 1, "ln_fold must be 0 or 1 (got %d)", value);
+      e->ln_fold = value != 0;
+      break;
     default:
       MQ_FAIL(MQ_EINVAL, "unknown encoder option %d", option);
   }
@@ -2778,6 +2973,7 @@ int mq_encoder_get_option(const mq_encoder* e, int option, int* value) {
     case MQ_ENC_OPT_SPLITK_TILES: *value = e->splitk_tiles; break;
     case MQ_ENC_OPT_X6_PRESPLIT: *value = e->x6_presplit ? 1 : 0; break;
     case MQ_ENC_OPT_ROWS_PLANES: *value = e->rows_planes ? 1 : 0; break;
+    case MQ_ENC_OPT_LN_FOLD: *value = e->ln_fold ? 1 : 0; break;
     default: MQ_FAIL(MQ_EINVAL, "unknown encoder option %d", option);
   }
   return MQ_OK;
@@ -2823,7 +3019,9 @@ int mq_encoder_embed(mq_encoder* e, const int32_t* ids, const int32_t* mask, int
   rc = e->slab.ensure((size_t)2 * e->num_cus * 32 * 128);
   if (rc) return rc;
   // y also holds the few-row forward's output-projection planes (<= 4 of M rows)
-  const size_t ln_parts = e->ln_on_load && M > 256 ? (size_t)4 * M * std::max(1, c.hidden / kLnPartW) : 0;
+  rc = build_fold(e);  // (MQ_ENC_OPT_LN_FOLD: the folded weights of the current mode, once)
+  if (rc) return rc;
+  const size_t ln_parts = (e->ln_on_load || e->ln_fold) && M > 256 ? (size_t)4 * M * std::max(1, c.hidden / kLnPartW) : 0;
   for (auto bn : {std::make_pair(&e->x, M * c.hidden), std::make_pair(&e->y, (M <= (size_t)kRowsMax ? 4 : 1) * M * c.hidden),
                   std::make_pair(&e->ctx, M * c.hidden), std::make_pair(&e->qkv, M * 3 * c.hidden),
                   // (the few-row FFN output is frag16: whole 16-row blocks)

@@ -162,7 +162,7 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
                                                              const float* __restrict__ bias,
                                                              const float* __restrict__ resid, int ldr,
                                                              float* __restrict__ out, int ldo, int M, int N,
-                                                             int K, int rx) {
+                                                             int K, int rx, LnFold lf) {
   __shared__ __attribute__((aligned(1024))) unsigned char lds[T::NBUF * T::STAGE];
   const unsigned lds0 = (unsigned)(uintptr_t)(x6p_lds_t*)lds;
   const int lane = threadIdx.x & 63;
@@ -556,7 +556,7 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
         int m0, n0;
         coords(c_i, m0, n0);
         store_wave_tile16<EPI, MB, NB16>(acc4, m0 + wm * T::WM, n0 + wn * T::WN, M, N, bias, resid, ldr, out, ldo,
-                                         lane);
+                                         lane, lf);
         zero4();
         ++c_i;
       }
@@ -684,9 +684,11 @@ template <class T, int EPI>
 void launch_t(const X6pArgs& g, int num_cus, hipStream_t s) {
   // stage depth must divide K: else the 16-deep 8-wave tile (32x32x16 arithmetic).  No caller
   // gets here: launch_gemm's K is a multiple of kBK = 32, as mq_debug_gemm_x6p's.
-  if (g.K % (16 * T::KS) != 0) {
-    launch_t<X6pTile<4, 2, 1, 3, 4>, EPI>(g, num_cus, s);
-    return;
+  if constexpr (EPI < EPI_RESID_LN_STATS) {
+    if (g.K % (16 * T::KS) != 0) {
+      launch_t<X6pTile<4, 2, 1, 3, 4>, EPI>(g, num_cus, s);
+      return;
+    }
   }
   const int tiles = ((g.M + T::BM - 1) / T::BM) * ((g.N + T::BN - 1) / T::BN);
   const int grid = (std::min(tiles, num_cus) + 7) / 8 * 8;  // one workgroup per CU, a multiple of 8
@@ -695,7 +697,8 @@ void launch_t(const X6pArgs& g, int num_cus, hipStream_t s) {
   if (rx < 0) rx = region_pick_rx(tiles_m, tiles_n, (double)T::BM * g.K * 4, (double)T::BN * g.K * 6, grid);
   if (rx > 0 && (8 % rx != 0 || rx > tiles_n || 8 / rx > tiles_m || grid < 8)) rx = 0;  // (a region per XCD)
   hipLaunchKernelGGL((gemm_x6p_kernel<T, EPI>), dim3(grid), dim3(T::THREADS), 0, s, g.A, g.lda,
-                     static_cast<const unsigned char*>(g.W3), g.bias, g.resid, g.ldr, g.out, g.ldo, g.M, g.N, g.K, rx);
+                     static_cast<const unsigned char*>(g.W3), g.bias, g.resid, g.ldr, g.out, g.ldo, g.M, g.N, g.K, rx,
+                     g.lf);
 }
 
 template <int EPI>
@@ -728,7 +731,51 @@ void launch_tile(const X6pArgs& g, int tile, int num_cus, hipStream_t s) {
   }
 }
 
+// the LayerNorm-fold epilogues: the default tiles only
+template <int EPI>
+void launch_tile_fold(const X6pArgs& g, int tile, int num_cus, hipStream_t s) {
+  if (tile == 1)
+    launch_t<X6p1, EPI>(g, num_cus, s);
+  else
+    launch_t<X6p0, EPI>(g, num_cus, s);
+}
+
+// one wave per weight row n: Wg[n][:] = g * W[n][:], s[n] and c[n] summed in float64
+__global__ __launch_bounds__(256) void ln_fold_weight_kernel(const float* __restrict__ W,
+                                                             const float* __restrict__ bias,
+                                                             const float* __restrict__ g,
+                                                             const float* __restrict__ b, int N, int K,
+                                                             float* __restrict__ Wg, float* __restrict__ s_out,
+                                                             float* __restrict__ c_out) {
+  const int lane = threadIdx.x & 63;
+  const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= N) return;
+  double sg = 0.0, sb = 0.0;
+  for (int k = lane; k < K; k += 64) {
+    const float w = W[(int64_t)n * K + k];
+    const float wg = g[k] * w;
+    Wg[(int64_t)n * K + k] = wg;
+    sg += (double)wg;
+    sb += (double)b[k] * (double)w;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    sg += __shfl_xor(sg, off);
+    sb += __shfl_xor(sb, off);
+  }
+  if (lane == 0) {
+    s_out[n] = (float)sg;
+    c_out[n] = (float)((double)bias[n] + sb);
+  }
+}
+
 }  // namespace
+
+void launch_ln_fold_weight(const float* W, const float* bias, const float* g, const float* b, int N, int K, float* Wg,
+                           float* s_out, float* c_out, hipStream_t s) {
+  hipLaunchKernelGGL(ln_fold_weight_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, s, W, bias, g, b, N, K, Wg,
+                     s_out, c_out);
+}
 
 void launch_split_w3(const float* W, int N, int K, void* w3, hipStream_t s) {
   const int64_t n = (int64_t)((N + 31) & ~31) * (K >> 3);
@@ -758,6 +805,10 @@ void launch_gemm_x6p(const X6pArgs& g, int epi, int tile, int num_cus, hipStream
     case EPI_GELU_ERF: launch_tile<EPI_GELU_ERF>(g, tile, num_cus, s); return;
     case EPI_GELU_TANH: launch_tile<EPI_GELU_TANH>(g, tile, num_cus, s); return;
     case EPI_RESID: launch_tile<EPI_RESID>(g, tile, num_cus, s); return;
+    case EPI_RESID_LN_STATS: launch_tile_fold<EPI_RESID_LN_STATS>(g, tile, num_cus, s); return;
+    case EPI_BIAS_LNFOLD: launch_tile_fold<EPI_BIAS_LNFOLD>(g, tile, num_cus, s); return;
+    case EPI_GELU_ERF_LNFOLD: launch_tile_fold<EPI_GELU_ERF_LNFOLD>(g, tile, num_cus, s); return;
+    case EPI_GELU_TANH_LNFOLD: launch_tile_fold<EPI_GELU_TANH_LNFOLD>(g, tile, num_cus, s); return;
     default: launch_tile<EPI_BIAS>(g, tile, num_cus, s); return;
   }
 }
@@ -796,6 +847,49 @@ int mq_debug_gemm_x6p(const float* A, const void* W3, const float* bias, const f
   X6pArgs g{A, K, W3, bias, resid, N, out, N, M, N, K};
   g.rx = rx;
   launch_gemm_x6p(g, epi, tile, cus, (hipStream_t)stream);
+  MQ_HIP(hipGetLastError());
+  return MQ_OK;
+}
+
+int mq_debug_ln_fold_weight(const float* W, const float* bias, const float* g, const float* b, int N, int K,
+                            float* Wg, float* s_out, float* c_out, void* stream) {
+  using namespace mq;
+  clear_error();
+  MQ_CHECK_ARG(W && bias && g && b && Wg && s_out && c_out, "NULL buffer");
+  MQ_CHECK_ARG(N > 0 && K > 0, "bad shape N=%d K=%d", N, K);
+  launch_ln_fold_weight(W, bias, g, b, N, K, Wg, s_out, c_out, (hipStream_t)stream);
+  MQ_HIP(hipGetLastError());
+  return MQ_OK;
+}
+
+int mq_debug_gemm_x6p_ln(const float* A, const void* W3, const float* bias, const float* resid, float* out, int M,
+                         int N, int K, int epi, int tile, const float* stats_in, float* stats_out, const float* g,
+                         const float* b, const float* s_fold, float eps, void* stream) {
+  using namespace mq;
+  clear_error();
+  MQ_CHECK_ARG(A && W3 && bias && out, "NULL buffer");
+  MQ_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 32 == 0, "bad shape M=%d N=%d K=%d", M, N, K);
+  MQ_CHECK_ARG(tile >= -1 && tile <= 1, "the LayerNorm-fold epilogues run on tiles 0 and 1 (got %d)", tile);
+  if (epi == EPI_RESID_LN_STATS) {
+    MQ_CHECK_ARG(resid && stats_out && (!stats_in || (g && b)), "producer: NULL buffer");
+    MQ_CHECK_ARG(N == kLnPartW * kLnMaxParts, "producer: N must be %d (got %d)", kLnPartW * kLnMaxParts, N);
+    MQ_CHECK_ARG((int64_t)M * N < (1ll << 29), "producer: M * N must stay below 2^29 (32-bit byte offsets)");
+  } else {
+    MQ_CHECK_ARG(epi_is_lnfold(epi), "epi must be a LayerNorm-fold kind (got %d)", epi);
+    MQ_CHECK_ARG(stats_in && s_fold, "consumer: NULL buffer");
+    MQ_CHECK_ARG(K == kLnPartW * kLnMaxParts, "consumer: K must be %d (got %d)", kLnPartW * kLnMaxParts, K);
+  }
+  int dev = 0, cus = 256;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  X6pArgs a{A, K, W3, bias, resid, N, out, N, M, N, K};
+  a.lf.stats_in = stats_in;
+  a.lf.stats_out = stats_out;
+  a.lf.g = g;
+  a.lf.b = b;
+  a.lf.s = s_fold;
+  a.lf.eps = eps;
+  launch_gemm_x6p(a, epi, tile, cus, (hipStream_t)stream);
   MQ_HIP(hipGetLastError());
   return MQ_OK;
 }

@@ -75,6 +75,29 @@ __host__ __device__ inline Region region_of(int rx, int xc, int tiles_m, int til
 // split W [N][K] fp32 (row stride K) into its W3 image (w3_bytes(N, K) bytes)
 void launch_split_w3(const float* W, int N, int K, void* w3, hipStream_t s);
 
+// LayerNorm folded into the split-f32 GEMMs ("LayerNorm folded into the
+// split-f32 GEMMs"; hidden = kLnPartW kLnMaxParts = 768).  A residual GEMM (the producer,
+// EPI_RESID_LN_STATS) writes the raw y = acc + bias + LN_prev(resid) and, per row and per
+// kLnPartW-column wave tile, the (mean, M2) partial of y: stats[row][part].  The GEMM that
+// consumes LN(y) (EPI_*_LNFOLD) multiplies the raw y by Wg = gamma W and applies
+//   LN(y) W^T + b = rho_r (y Wg^T - mu_r s) + c,  s[n] = sum_k Wg[n,k],  c[n] = b[n] + sum_k beta_k W[n,k]
+// in its epilogue, (mu_r, rho_r) merged from the row's partials (gemm_epi.hpp ln_merge).
+constexpr int kLnPartW = 96;    // columns per partial: the producers' wave tile
+constexpr int kLnMaxParts = 8;  // partials per row
+struct LnFold {
+  const float* stats_in = nullptr;  // consumer: A's rows; producer: the residual's rows (null: the
+                                    // residual is already normalised and taken as it is)
+  float* stats_out = nullptr;       // producer: the partials of its output rows
+  const float* g = nullptr;         // producer: gamma / beta [N] of the residual's LayerNorm
+  const float* b = nullptr;
+  const float* s = nullptr;         // consumer: s[N] (c[N] goes in as the bias)
+  float eps = 0.f;
+};
+// Wg[n][k] = g[k] W[n][k] (rounded to fp32), s[n] = sum_k Wg[n][k] and c[n] = bias[n] +
+// sum_k b[k] W[n][k], both sums in float64 from the rounded values
+void launch_ln_fold_weight(const float* W, const float* bias, const float* g, const float* b, int N, int K, float* Wg,
+                           float* s_out, float* c_out, hipStream_t s);
+
 struct X6pArgs {
   const float* A;  // [M][lda] fp32 activations
   int lda;
@@ -86,6 +109,7 @@ struct X6pArgs {
   int ldo;
   int M, N, K;  // K % 16 == 0
   int rx = -1;  // tile-walk region split (gemm_x6p.hip x6p_pick_rx): -1 = the pick, 0 = none, 1/2/4/8
+  LnFold lf{};  // the EPI_RESID_LN_STATS / EPI_*_LNFOLD epilogues
 };
 
 // Tile shapes (workgroups of 8 waves, one per CU): 0 = 128 x 192 (4 compute + 4 loader
@@ -95,7 +119,8 @@ struct X6pArgs {
 // ahead (measurement); 16 / 17 are tiles 0 / 7 on the former 32x32x16 k-step (measurement;
 // fp32-class, not bit-identical to the others).  -1 = the pick below.
 int x6p_pick_tile(int M, int N, int num_cus);
-// epi: EPI_BIAS / EPI_GELU_ERF / EPI_GELU_TANH / EPI_RESID (gemm_epi.hpp)
+// epi: EPI_BIAS / EPI_GELU_ERF / EPI_GELU_TANH / EPI_RESID (gemm_epi.hpp); the LayerNorm-fold
+// kinds (g.lf) on tiles 0 and 1 only, K % 32 == 0
 void launch_gemm_x6p(const X6pArgs& g, int epi, int tile, int num_cus, hipStream_t s);
 
 }  // namespace mq

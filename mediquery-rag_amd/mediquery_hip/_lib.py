@@ -28,6 +28,7 @@ MQ_ENC_OPT_LN_ROWS_PER_WAVE, MQ_ENC_OPT_FUSE_ATTN_OPROJ, MQ_ENC_OPT_FUSED_LN = 3
 MQ_ENC_OPT_SPLITK_TILES, MQ_ENC_OPT_LN_ON_LOAD, MQ_ENC_OPT_RESIDENT_LAYERS = 6, 7, 8
 MQ_ENC_OPT_X6_PRESPLIT = 9
 MQ_ENC_OPT_ROWS_PLANES = 10
+MQ_ENC_OPT_LN_FOLD = 11
 
 
 class MQError(RuntimeError):
@@ -114,6 +115,8 @@ SIGNATURES = {
     "mq_debug_w3_bytes": (_I64, [_I, _I]),
     "mq_debug_split_w3": (_I, [_P, _I, _I, _P, _P]),
     "mq_debug_gemm_x6p": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "mq_debug_gemm_x6p_ln": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_float, _P]),
+    "mq_debug_ln_fold_weight": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "mq_debug_int8_screen": (_I, [_P, _P, _I, _P, _P, _P]),
 }
 

@@ -267,7 +267,7 @@ class Encoder:
                "fuse_attn_oproj": _lib.MQ_ENC_OPT_FUSE_ATTN_OPROJ, "fused_ln": _lib.MQ_ENC_OPT_FUSED_LN,
                "splitk_tiles": _lib.MQ_ENC_OPT_SPLITK_TILES, "ln_on_load": _lib.MQ_ENC_OPT_LN_ON_LOAD,
                "resident_layers": _lib.MQ_ENC_OPT_RESIDENT_LAYERS, "x6_presplit": _lib.MQ_ENC_OPT_X6_PRESPLIT,
-               "rows_planes": _lib.MQ_ENC_OPT_ROWS_PLANES}
+               "rows_planes": _lib.MQ_ENC_OPT_ROWS_PLANES, "ln_fold": _lib.MQ_ENC_OPT_LN_FOLD}
 
     def set_option(self, name, value):
         """Tuning option of the forward (mq_encoder_set_option): rows_max, rows_splits,

@@ -91,8 +91,65 @@ def ab(a, dev, st):
                 out_f.flush()
 
 
+def ln_fold(a, dev, st):
+    """--ln-fold: per shape, the plain K2p launch against the same launch with its LayerNorm-fold
+    epilogue (mq_debug_gemm_x6p_ln: the producer, epi 5, for the residual shapes, the
+    consumers, epi 6 / 7 / 8, for the others), alternating `--reps` times on the default
+    tile; one JSON line per shape with every round's us per launch."""
+    out_f = open(a.out, "a") if a.out else None
+    for name in a.shapes.split(","):
+        M, N, K, epi = SHAPES[name]
+        g = torch.Generator(device=dev).manual_seed(1)
+        A = torch.randn(M, K, device=dev, generator=g)
+        W = torch.randn(N, K, device=dev, generator=g) * 0.05
+        b = torch.randn(N, device=dev, generator=g)
+        R = torch.randn(M, N, device=dev, generator=g)
+        out = torch.empty(M, N, device=dev)
+        gam = torch.ones(max(N, K), device=dev)
+        bet = torch.zeros(max(N, K), device=dev)
+        s_fold = torch.zeros(N, device=dev)
+        stats_in = torch.zeros(M, 8, 2, device=dev)
+        stats_in[:, :, 1] = 96.0
+        stats_out = torch.empty(M, 8, 2, device=dev)
+        w3 = torch.empty(_lib.lib().mq_debug_w3_bytes(N, K), dtype=torch.uint8, device=dev)
+        _lib.call("mq_debug_split_w3", _lib.ptr(W), N, K, _lib.ptr(w3), st)
+        fepi = 5 if epi == 3 else 6 + epi
+
+        def plain():
+            _lib.call("mq_debug_gemm_x6p", _lib.ptr(A), _lib.ptr(w3), _lib.ptr(b), _lib.ptr(R), _lib.ptr(out),
+                      M, N, K, epi, -1, st)
+
+        def fold():
+            _lib.call("mq_debug_gemm_x6p_ln", _lib.ptr(A), _lib.ptr(w3), _lib.ptr(b), _lib.ptr(R), _lib.ptr(out),
+                      M, N, K, fepi, -1, _lib.ptr(stats_in), _lib.ptr(stats_out), _lib.ptr(gam), _lib.ptr(bet),
+                      _lib.ptr(s_fold), 1e-12, st)
+
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        rounds = {"plain": [], "fold": []}
+        for fn in (plain, fold):
+            for _ in range(3):
+                fn()
+        for _ in range(a.reps):
+            for key, fn in (("plain", plain), ("fold", fold)):
+                e0.record()
+                for _ in range(a.iters):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                rounds[key].append(round(e0.elapsed_time(e1) * 1000.0 / a.iters, 2))
+        med = {k: sorted(v)[len(v) // 2] for k, v in rounds.items()}
+        line = json.dumps({"shape": name, "M": M, "N": N, "K": K, "epi": epi, "fold_epi": fepi,
+                           "plain_us": rounds["plain"], "fold_us": rounds["fold"], "plain_med": med["plain"],
+                           "fold_med": med["fold"], "fold_minus_plain_us": round(med["fold"] - med["plain"], 2)})
+        print(line, flush=True)
+        if out_f:
+            out_f.write(line + "\n")
+            out_f.flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ln-fold", action="store_true", help="plain vs LayerNorm-fold epilogue per shape (see ln_fold())")
     ap.add_argument("--ab", default="", help="OLD:NEW tile code pairs to time alternating (see ab())")
     ap.add_argument("--out", default="", help="--ab: also append the JSON lines to this file")
     ap.add_argument("--check", action="store_true", help="--ab: bias epilogue, report max |err| vs float64")
@@ -108,6 +165,9 @@ def main():
     st = _lib.stream_handle()
     if a.ab:
         ab(a, dev, st)
+        return
+    if a.ln_fold:
+        ln_fold(a, dev, st)
         return
     for name in a.shapes.split(","):
         M, N, K, epi = SHAPES[name]
