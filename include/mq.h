@@ -368,8 +368,10 @@ int mq_debug_split_w3(const float* W, int N, int K, void* w3, void* stream);
  * Asynchronous on `stream`.  K % 32 == 0. */
 int mq_debug_gemm_x6p(const float* A, const void* W3, const float* bias, const float* resid,
                       float* out, int M, int N, int K, int epi, int tile, void* stream);
-/* One K2p launch with a LayerNorm-fold epilogue (tile 0, 1 or -1 = the pick; no fill-the-chip
- * gate).  epi 5 = the producer: out = acc + bias + LN(resid) with the residual normalised from
+/* One K2p launch with a LayerNorm-fold epilogue (tile 0, 1 or -1 = the pick; 20 / 21 = tiles
+ * 0 / 1 with the producer's former epilogue - its own residual loads on every tile, no
+ * loader-wave hand-off - bit-identical, kept for measurement; no fill-the-chip gate).
+ * epi 5 = the producer: out = acc + bias + LN(resid) with the residual normalised from
  * stats_in [M][8] (mean, M2) pairs and g / b [N] (stats_in NULL: the residual as it is), and
  * the partials of out written to stats_out [M][8]; N = 768.  epi 6 / 7 / 8 = the consumers
  * (bias / GELU erf / GELU tanh): out = epi(rho_r (acc - mu_r s_fold[n]) + bias[n]), (mu, rho)

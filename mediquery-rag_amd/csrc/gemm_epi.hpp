@@ -188,18 +188,31 @@ __device__ __forceinline__ void store_wave_tile(floatx16 (&acc)[TM][TN], int wr0
 // 1 for the loads, stores predicated on row < M: one path for whole and ragged tiles; byte
 // offsets are 32-bit, M ld < 2^29); ER rows of a block row are loaded, finished and stored at
 // a time.
+//
+// HAND (K2p's loader-wave hand-off, gemm_x6p.hip): the normalised residual t = (r - mu) rho (r
+// itself without stats_in) of the wave tile already lies in LDS at `tl`, written by the
+// partner loader wave in accumulator order (ln_tile_write below) - one ds_read_b128 per block,
+// no residual or stats_in traffic here; the same v = fma(t, gamma, acc + bias + beta) and the
+// same partials, bit for bit.
 typedef unsigned uint2v_t __attribute__((ext_vector_type(2)));
-template <int ER, int MB, int NB>
+// byte offset of lane l's four rows 4 (l >> 4) + e of column l & 15 inside a block's 1 KB of t:
+// the 16-B slot of column c of row group g is c ^ g, so that the writer's ds_write_b32 (lanes
+// that differ in g hold the same column) and this read are both free of bank conflicts
+__device__ __forceinline__ unsigned ln_t_slot(int lane) { return 16u * (unsigned)(lane ^ (lane >> 4)); }
+template <int ER, int MB, int NB, bool HAND = false>
 __device__ __forceinline__ void store_wave_tile16_ln_stats(floatx4 (&acc)[MB][NB], int wr0, int wc0, int M,
                                                            const float* __restrict__ bias,
                                                            const float* __restrict__ resid, int ldr,
                                                            float* __restrict__ out, int ldo, int lane,
-                                                           const LnFold& lf) {
+                                                           const LnFold& lf, const unsigned char* tl = nullptr) {
   static_assert(NB * 16 == kLnPartW && MB <= 4, "partials are per kLnPartW-column wave tile");
+  static_assert(!HAND || ER == 1, "the hand-off form finishes a row at a time");
   const int c = lane & 15, g = lane >> 4;
   const bool ln_r = lf.stats_in != nullptr;  // (kernel-uniform)
   float own_mu = 0.f, own_rho = 1.0f;        // this lane's row of the residual (ln_row_own)
-  if (ln_r) ln_row_own<MB>(lf.stats_in, wr0, M, lf.eps, lane, own_mu, own_rho);
+  if constexpr (!HAND) {
+    if (ln_r) ln_row_own<MB>(lf.stats_in, wr0, M, lf.eps, lane, own_mu, own_rho);
+  }
   // bias + beta goes into the accumulators in place and only gamma stays live (the kernels
   // around this store sit at the register limit)
   float gv[NB];
@@ -220,26 +233,41 @@ __device__ __forceinline__ void store_wave_tile16_ln_stats(floatx4 (&acc)[MB][NB
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(lf.stats_out + 2 * (wc0 / kLnPartW)), (short)0, 0x7fffffff, 0x00020000);
 #pragma unroll
-  for (int m = 0; m < MB; ++m)
+  for (int m = 0; m < MB; ++m) {
+    floatx4 tv[NB];
+    if constexpr (HAND) {
+#pragma unroll
+      for (int n = 0; n < NB; ++n)
+        tv[n] = *reinterpret_cast<const floatx4*>(tl + (m * NB + n) * 1024 + ln_t_slot(lane));
+    }
 #pragma unroll
     for (int eh = 0; eh < 4; eh += ER) {
       float v[ER][NB];
+      if constexpr (!HAND) {
 #pragma unroll
-      for (int e2 = 0; e2 < ER; ++e2) {
-        const int lo = (min(wr0 + m * 16 + 4 * g + eh + e2, M - 1) * ldr + c) * 4;
+        for (int e2 = 0; e2 < ER; ++e2) {
+          const int lo = (min(wr0 + m * 16 + 4 * g + eh + e2, M - 1) * ldr + c) * 4;
 #pragma unroll
-        for (int n = 0; n < NB; ++n)
-          v[e2][n] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr, lo, n * 64, 0));
+          for (int n = 0; n < NB; ++n)
+            v[e2][n] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rr, lo, n * 64, 0));
+        }
       }
 #pragma unroll
       for (int e2 = 0; e2 < ER; ++e2) {
         const int e = eh + e2, row = wr0 + m * 16 + 4 * g + e;
-        const float mu = ln_row_bcast(own_mu, lane, m, e), rho = ln_row_bcast(own_rho, lane, m, e);
+        float mu = 0.f, rho = 1.0f;
+        if constexpr (!HAND) {
+          mu = ln_row_bcast(own_mu, lane, m, e);
+          rho = ln_row_bcast(own_rho, lane, m, e);
+        }
         const int so = (row * ldo + c) * 4;
         float sum = 0.f;
 #pragma unroll
         for (int n = 0; n < NB; ++n) {
-          v[e2][n] = __fmaf_rn((v[e2][n] - mu) * rho, gv[n], acc[m][n][e]);
+          if constexpr (HAND)
+            v[e2][n] = __fmaf_rn(tv[n][e], gv[n], acc[m][n][e]);
+          else
+            v[e2][n] = __fmaf_rn((v[e2][n] - mu) * rho, gv[n], acc[m][n][e]);
           sum += v[e2][n];
           if (row < M) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[e2][n]), ro, so, n * 64, 0);
         }
@@ -259,6 +287,68 @@ __device__ __forceinline__ void store_wave_tile16_ln_stats(floatx4 (&acc)[MB][NB
         }
       }
     }
+  }
+}
+
+// The loader wave's side of the hand-off: the residual of an MB x NB block wave tile, one
+// 16x16 block per 16-byte row-major load instruction (lane -> row lane >> 2, columns 4 (lane &
+// 3) .. + 3; rows clamped to M - 1 as the epilogue's loads are; N is a multiple of the wave
+// tile's width), and the (mean, M2) partials of one of the lane's MB = 4 rows, that of block
+// row lane & 3 (the four lanes of a quad hold the same row of every block row: each merges one
+// and a quad broadcast hands it round); then t = (r - mu) rho, with (mu, rho) from the same
+// ln_merge as every other user (mu = 0, rho = 1 without stats_in: t is r, as in the global-load
+// epilogue), written in accumulator order (ln_t_slot).
+template <int MB, int NB>
+struct LnTileRegs {
+  floatx4 r[MB][NB];
+  floatx4 p[kLnMaxParts / 2];
+};
+template <int Q>
+__device__ __forceinline__ float quad_bcast(float v) {  // lane Q of each quad
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), Q * 0x55, 0xF, 0xF, false));
+}
+template <int MB, int NB>
+__device__ __forceinline__ void ln_tile_load(LnTileRegs<MB, NB>& q, const float* __restrict__ resid, int ldr,
+                                             int wr0, int wc0, int M, const LnFold& lf, int lane) {
+  const __amdgpu_buffer_rsrc_t rr =
+      __builtin_amdgcn_make_buffer_rsrc((void*)(resid + wc0), (short)0, 0x7fffffff, 0x00020000);
+#pragma unroll
+  for (int m = 0; m < MB; ++m) {
+    const int row = min(wr0 + m * 16 + (lane >> 2), M - 1);
+    const int lo = (row * ldr + 4 * (lane & 3)) * 4;
+#pragma unroll
+    for (int n = 0; n < NB; ++n)
+      q.r[m][n] = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(rr, lo, n * 64, 0));
+  }
+  if (lf.stats_in != nullptr) {
+    const int row = min(wr0 + (lane & 3) * 16 + (lane >> 2), M - 1);
+    const floatx4* src = reinterpret_cast<const floatx4*>(lf.stats_in + (int64_t)row * (2 * kLnMaxParts));
+#pragma unroll
+    for (int i = 0; i < kLnMaxParts / 2; ++i) q.p[i] = src[i];
+  }
+}
+template <int MB, int NB>
+__device__ __forceinline__ void ln_tile_write(const LnTileRegs<MB, NB>& q, unsigned char* tl, const LnFold& lf,
+                                              int lane) {
+  static_assert(MB == 4, "a quad's lanes share out the block rows");
+  const int g = lane >> 4, e = (lane >> 2) & 3;
+  unsigned off[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) off[i] = (unsigned)(256 * g + 16 * ((4 * (lane & 3) + i) ^ g) + 4 * e);
+  float own_mu = 0.f, own_rho = 1.0f;
+  if (lf.stats_in != nullptr) ln_merge(q.p, lf.eps, own_mu, own_rho);
+  const float mus[4] = {quad_bcast<0>(own_mu), quad_bcast<1>(own_mu), quad_bcast<2>(own_mu), quad_bcast<3>(own_mu)};
+  const float rhos[4] = {quad_bcast<0>(own_rho), quad_bcast<1>(own_rho), quad_bcast<2>(own_rho),
+                         quad_bcast<3>(own_rho)};
+#pragma unroll
+  for (int m = 0; m < MB; ++m) {
+    const float mu = mus[m], rho = rhos[m];
+#pragma unroll
+    for (int n = 0; n < NB; ++n)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        *reinterpret_cast<float*>(tl + (m * NB + n) * 1024 + off[i]) = (q.r[m][n][i] - mu) * rho;
+  }
 }
 
 template <int EPI, int MB, int NB>

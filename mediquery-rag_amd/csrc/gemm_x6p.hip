@@ -156,7 +156,37 @@ struct X6pTile {
   static_assert(AHEAD >= 2 && NBUF * STAGE <= 160 * 1024, "LDS ring");
 };
 
-template <class T, int EPI>
+// FORMER (tile codes 20 / 21 of mq_debug_gemm_x6p_ln): the producer's epilogue as it was before
+// the loader-wave hand-off - its own global loads on every tile - kept to re-measure the two in
+// one library.  Same results, bit for bit.
+//
+// The producer's hand-off (HAND: EPI_RESID_LN_STATS on the loader-wave tiles X6p0 / X6p1).  On
+// the workgroup's LAST tile the loader wave prepares its SIMD partner's residual during the
+// final k-stages: it loads the partner's 64 x 96 wave tile of the residual and its rows'
+// partials (ln_tile_load), forms t = (r - mu) rho and writes it to LDS in accumulator order
+// (ln_tile_write); after one more barrier the compute wave finishes its rows from LDS
+// (store_wave_tile16_ln_stats<.., HAND>), with no residual or stats_in round trips of its own.
+// Tiles before the last keep the global-load epilogue: the ring is carrying the next tile's
+// prefetch then, and no slot is free.
+//   Slot plan (S stages, stage k in slot k % 3, ring two stages ahead).  The loader's DMAs of
+//   "stages" S and S + 1 (re-reads of the last stage, never multiplied) are not issued.  After
+//   barrier B(S) (below) slot S % 3 holds stage S - 3, multiplied two iterations ago (S = 1: the
+//   prologue's re-read of stage 0, landed; S = 2: nothing), and slot (S + 1) % 3 holds stage
+//   S - 2, whose multiplies every compute wave finished before it arrived at B(S).  Slot
+//   (S - 1) % 3 holds the last stage and is not touched.  t (4 waves x 24 KB) goes to those
+//   two slots, waves 0 - 1 to the first, 2 - 3 to the second (2 x 24 KB <= STAGE).  The compute
+//   waves' never-multiplied reads of "stage S" in the last iteration come from slot S % 3 and
+//   return whatever is there: those registers are dead.
+//   Barriers, per role (every wave of the workgroup executes each exactly once):
+//                         compute waves                      loader waves
+//     prologue  B(0)      before reading stage 0             after vmcnt: stage 0 landed
+//     stage j   B(j + 1)  top of iteration j, j < S          stage j + 1 landed, j < S
+//     hand-off  B(S + 1)  after iteration S - 1's MFMAs      after t is written, lgkmcnt(0)
+//   i.e. S + 2 on both sides.  The loader issues the residual loads after B(S - 1) (S = 1:
+//   after B(0)), when none of its DMAs is left to issue: the vmcnt(0) in front of B(S) covers
+//   them, and at most 13 DMAs + 24 + 4 loads are outstanding.  It writes t between B(S) and
+//   B(S + 1), beside the last stage's MFMAs.
+template <class T, int EPI, bool FORMER = false>
 __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __restrict__ A, int lda,
                                                              const unsigned char* __restrict__ W3,
                                                              const float* __restrict__ bias,
@@ -165,6 +195,9 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
                                                              int K, int rx, LnFold lf) {
   __shared__ __attribute__((aligned(1024))) unsigned char lds[T::NBUF * T::STAGE];
   const unsigned lds0 = (unsigned)(uintptr_t)(x6p_lds_t*)lds;
+  constexpr bool HAND = EPI == EPI_RESID_LN_STATS && T::LDR && T::M16 && !T::DEEP && T::NBUF == 3 && !FORMER;
+  static_assert(!HAND || (T::NW == 4 && 2 * T::WM * T::WN * 4 <= T::STAGE && T::WN == kLnPartW && T::STAGE % 1024 == 0),
+                "hand-off: two wave tiles of t per ring slot");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int cw = T::LDR ? wave % T::NW : wave;  // compute wave index
@@ -435,6 +468,25 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
 #pragma unroll
       for (int d = 0; d < T::AHEAD; ++d) issue(d);
       wait_stages(IC<T::AHEAD - 1>{});  // stage 0 landed
+      if constexpr (HAND) {
+        // (the kernel's comment has the slot plan and the barrier table)
+        static_assert(T::AHEAD == 2, "hand-off: the ring two stages ahead");
+        for (int j = 0; j + 2 < S; ++j) {
+          wait_stages(IC<0>{});      // B(j + 1): stage j + 1 landed
+          issue((j + 2) % T::NBUF);  // stage j + 2 <= S - 1
+        }
+        if (S >= 2) wait_stages(IC<0>{});  // B(S - 1)
+        int m0, n0;
+        coords(n_tiles - 1, m0, n0);
+        LnTileRegs<2 * T::TM, 2 * T::TN> q;
+        ln_tile_load(q, resid, ldr, m0 + wm * T::WM, n0 + wn * T::WN, M, lf, lane);
+        wait_stages(IC<0>{});  // B(S): vmcnt(0), the last stage and the residual have landed
+        const int ts = (S + (cw >> 1)) % T::NBUF;
+        ln_tile_write(q, lds + ts * T::STAGE + (cw & 1) * (T::WM * T::WN * 4), lf, lane);
+        __builtin_amdgcn_s_waitcnt(0xC07F);       // t is in LDS
+        asm volatile("s_barrier" ::: "memory");  // B(S + 1): the hand-off
+        return;
+      }
       for (int j = 0; j < S; ++j) {
         wait_stages(IC<T::AHEAD - 2>{});  // stage j + 1 landed
         issue((j + T::AHEAD) % T::NBUF);  // stage j + AHEAD
@@ -529,6 +581,10 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
         if constexpr (T::DEEP) __builtin_amdgcn_s_waitcnt(0xC07F);
         asm volatile("s_barrier" ::: "memory");
       }
+      // (HAND, last iteration: slot rb = S % 3 holds no stage - the loader waves are writing t
+      // into it while these reads of "stage S" run.  The race is benign only because what the
+      // reads return is never multiplied: raw, au and bw are dead after this iteration and
+      // must stay so)
       const unsigned char* st = lds + rb * T::STAGE;
       static_for<NM16>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
@@ -552,6 +608,9 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
       }
       rb = rb + 1 == T::NBUF ? 0 : rb + 1;
       if (++c_st == nst) {
+        if constexpr (HAND) {
+          if (j == S - 1) break;  // the workgroup's last tile: finished below, from LDS
+        }
         c_st = 0;
         int m0, n0;
         coords(c_i, m0, n0);
@@ -560,6 +619,16 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
         zero4();
         ++c_i;
       }
+    }
+    if constexpr (HAND) {
+      asm volatile("s_barrier" ::: "memory");  // B(S + 1): the loader waves have written t
+      int m0, n0;
+      coords(n_tiles - 1, m0, n0);
+      const int ts = (S + (cw >> 1)) % T::NBUF;
+      store_wave_tile16_ln_stats<1, MB, NB16, true>(acc4, m0 + wm * T::WM, n0 + wn * T::WN, M, bias, resid, ldr, out,
+                                                    ldo, lane, lf,
+                                                    lds + ts * T::STAGE + (cw & 1) * (T::WM * T::WN * 4));
+      return;
     }
     if constexpr (!T::LDR) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing re-read DMAs
     return;
@@ -680,7 +749,7 @@ using X6p7 = X6pTile<2, 2, 1, 3, 3, 2, 4, true, 0, 1, 0, 6, true, true>;        
 using X6p16 = X6pTile<2, 2, 2, 3, 4, 1, 4, true, 0, 1, 0, 6, true>;
 using X6p17 = X6pTile<2, 2, 1, 3, 4, 1, 4, true, 0, 1, 0, 6, true>;
 
-template <class T, int EPI>
+template <class T, int EPI, bool FORMER = false>
 void launch_t(const X6pArgs& g, int num_cus, hipStream_t s) {
   // stage depth must divide K: else the 16-deep 8-wave tile (32x32x16 arithmetic).  No caller
   // gets here: launch_gemm's K is a multiple of kBK = 32, as mq_debug_gemm_x6p's.
@@ -696,7 +765,7 @@ void launch_t(const X6pArgs& g, int num_cus, hipStream_t s) {
   int rx = g.rx;
   if (rx < 0) rx = region_pick_rx(tiles_m, tiles_n, (double)T::BM * g.K * 4, (double)T::BN * g.K * 6, grid);
   if (rx > 0 && (8 % rx != 0 || rx > tiles_n || 8 / rx > tiles_m || grid < 8)) rx = 0;  // (a region per XCD)
-  hipLaunchKernelGGL((gemm_x6p_kernel<T, EPI>), dim3(grid), dim3(T::THREADS), 0, s, g.A, g.lda,
+  hipLaunchKernelGGL((gemm_x6p_kernel<T, EPI, FORMER>), dim3(grid), dim3(T::THREADS), 0, s, g.A, g.lda,
                      static_cast<const unsigned char*>(g.W3), g.bias, g.resid, g.ldr, g.out, g.ldo, g.M, g.N, g.K, rx,
                      g.lf);
 }
@@ -731,13 +800,17 @@ void launch_tile(const X6pArgs& g, int tile, int num_cus, hipStream_t s) {
   }
 }
 
-// the LayerNorm-fold epilogues: the default tiles only
+// the LayerNorm-fold epilogues: the default tiles only; 20 / 21 = tiles 0 / 1 with the producer's
+// former epilogue (no hand-off; the consumers have one form)
 template <int EPI>
 void launch_tile_fold(const X6pArgs& g, int tile, int num_cus, hipStream_t s) {
-  if (tile == 1)
-    launch_t<X6p1, EPI>(g, num_cus, s);
-  else
-    launch_t<X6p0, EPI>(g, num_cus, s);
+  constexpr bool HAS_FORMER = EPI == EPI_RESID_LN_STATS;
+  switch (tile) {
+    case 1: launch_t<X6p1, EPI>(g, num_cus, s); return;
+    case 20: launch_t<X6p0, EPI, HAS_FORMER>(g, num_cus, s); return;
+    case 21: launch_t<X6p1, EPI, HAS_FORMER>(g, num_cus, s); return;
+    default: launch_t<X6p0, EPI>(g, num_cus, s); return;
+  }
 }
 
 // one wave per weight row n: Wg[n][:] = g * W[n][:], s[n] and c[n] summed in float64
@@ -869,7 +942,8 @@ int mq_debug_gemm_x6p_ln(const float* A, const void* W3, const float* bias, cons
   clear_error();
   MQ_CHECK_ARG(A && W3 && bias && out, "NULL buffer");
   MQ_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 32 == 0, "bad shape M=%d N=%d K=%d", M, N, K);
-  MQ_CHECK_ARG(tile >= -1 && tile <= 1, "the LayerNorm-fold epilogues run on tiles 0 and 1 (got %d)", tile);
+  MQ_CHECK_ARG((tile >= -1 && tile <= 1) || tile == 20 || tile == 21,
+               "the LayerNorm-fold epilogues run on tiles 0 and 1 (20 / 21: their former epilogues; got %d)", tile);
   if (epi == EPI_RESID_LN_STATS) {
     MQ_CHECK_ARG(resid && stats_out && (!stats_in || (g && b)), "producer: NULL buffer");
     MQ_CHECK_ARG(N == kLnPartW * kLnMaxParts, "producer: N must be %d (got %d)", kLnPartW * kLnMaxParts, N);

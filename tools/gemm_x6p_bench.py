@@ -41,7 +41,13 @@ def timed(fn, iters):
 def ab(a, dev, st):
     """--ab OLD:NEW[,OLD:NEW...]: per shape, time the two K2p tile codes of each pair in one
     process, alternating (old, new, old, new, ...) `--reps` times on the same random
-    operands; one JSON line per (shape, pair) with every round's us per launch."""
+    operands; one JSON line per (shape, pair) with every round's us per launch and each arm's
+    round-to-round spread (max - min over its median).  With --ln-fold the launches carry the
+    LayerNorm-fold epilogues (mq_debug_gemm_x6p_ln: the producer, epi 5 with stats_in, for the
+    residual shapes, the consumers 6 / 7 / 8 for the others), e.g. --ab 20:0 for the producer's
+    former epilogue against the loader-wave hand-off on tile 0.  Codes 20 / 21 differ from 0 / 1
+    on the producer shapes (out_proj, ffn_down) only: a pair that names them skips the others
+    (it would time one kernel twice)."""
     pairs = [tuple(int(t) for t in p.split(":")) for p in a.ab.split(",")]
     out_f = open(a.out, "a") if a.out else None
     for name in a.shapes.split(","):
@@ -55,17 +61,34 @@ def ab(a, dev, st):
         w3 = torch.empty(_lib.lib().mq_debug_w3_bytes(N, K), dtype=torch.uint8, device=dev)
         _lib.call("mq_debug_split_w3", _lib.ptr(W), N, K, _lib.ptr(w3), st)
         ref = A.double() @ W.double().T + b.double() if a.check else None
+        fepi = 5 if epi == 3 else 6 + epi
+        if a.ln_fold and fepi != 5:
+            pairs_here = [p for p in pairs if not {20, 21} & set(p)]
+        else:
+            pairs_here = pairs
+        if a.ln_fold:
+            gam = torch.ones(max(N, K), device=dev)
+            bet = torch.zeros(max(N, K), device=dev)
+            s_fold = torch.zeros(N, device=dev)
+            stats_in = torch.zeros(M, 8, 2, device=dev)
+            stats_in[:, :, 1] = 96.0
+            stats_out = torch.empty(M, 8, 2, device=dev)
 
         def run(t):
+            if a.ln_fold:
+                _lib.call("mq_debug_gemm_x6p_ln", _lib.ptr(A), _lib.ptr(w3), _lib.ptr(b), _lib.ptr(R), _lib.ptr(out),
+                          M, N, K, fepi, t, _lib.ptr(stats_in), _lib.ptr(stats_out), _lib.ptr(gam), _lib.ptr(bet),
+                          _lib.ptr(s_fold), 1e-12, st)
+                return
             _lib.call("mq_debug_gemm_x6p", _lib.ptr(A), _lib.ptr(w3), _lib.ptr(b), _lib.ptr(R), _lib.ptr(out),
                       M, N, K, 0 if a.check else epi, t, st)
 
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for old, new in pairs:
+        for old, new in pairs_here:
             rounds = {old: [], new: []}
             err = {}
             for t in (old, new):
-                for _ in range(3):
+                for _ in range(a.iters if a.ln_fold else 3):  # (a whole untimed round: the clock settles)
                     run(t)
                 if ref is not None:
                     torch.cuda.synchronize()
@@ -79,7 +102,10 @@ def ab(a, dev, st):
                     torch.cuda.synchronize()
                     rounds[t].append(round(e0.elapsed_time(e1) * 1000.0 / a.iters, 2))
             med = {t: sorted(v)[len(v) // 2] for t, v in rounds.items()}
-            line = json.dumps({"shape": name, "M": M, "N": N, "K": K, "old_tile": old, "new_tile": new,
+            spread = {t: round((max(v) - min(v)) / med[t], 4) for t, v in rounds.items()}
+            line = json.dumps({"shape": name, "M": M, "N": N, "K": K, "epi": fepi if a.ln_fold else epi,
+                               "old_tile": old, "new_tile": new, "old_spread": spread[old],
+                               "new_spread": spread[new],
                                "old_us": rounds[old], "new_us": rounds[new], "old_med": med[old],
                                "new_med": med[new], "old_over_new": round(med[old] / med[new], 4),
                                "old_tflops": round(2.0 * M * N * K / med[old] / 1e6, 1),
@@ -149,7 +175,9 @@ def ln_fold(a, dev, st):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--ln-fold", action="store_true", help="plain vs LayerNorm-fold epilogue per shape (see ln_fold())")
+    ap.add_argument("--ln-fold", action="store_true",
+                    help="plain vs LayerNorm-fold epilogue per shape (see ln_fold()); with --ab: the pairs on the "
+                         "LayerNorm-fold epilogues")
     ap.add_argument("--ab", default="", help="OLD:NEW tile code pairs to time alternating (see ab())")
     ap.add_argument("--out", default="", help="--ab: also append the JSON lines to this file")
     ap.add_argument("--check", action="store_true", help="--ab: bias epilogue, report max |err| vs float64")
