@@ -383,6 +383,26 @@ int mq_debug_gemm_x6p_ln(const float* A, const void* W3, const float* bias, cons
                          float eps, void* stream);
 int mq_debug_ln_fold_weight(const float* W, const float* bias, const float* g, const float* b, int N,
                             int K, float* Wg, float* s_out, float* c_out, void* stream);
+/* One attention launch (K3) on device buffers: ctx [B*L][H] = softmax(scale Q K^T over the
+ * keys with mask != 0) V per (sequence, head); a query whose keys are all masked gives 0.
+ * qkv is [B*L][3H] row-major, Q | K | V columns, head h at column h * 64 of each third
+ * (H == heads * 64); mask is [B*L] int32.  variant -1 = the forward's own pick; 1 / 2 / 4 / 8 =
+ * attention_kernel with that many key-split waves; 12 = one workgroup of 12 head waves
+ * (heads == 12, L <= 32); 16 = attention_rows_kernel (L <= 64).  The product's kernels,
+ * unchanged.  Asynchronous on `stream`. */
+int mq_debug_attention(const float* qkv, const int* mask, int B, int L, int H, int heads, float scale,
+                       int variant, float* ctx, void* stream);
+/* The few-row forward's fused attention + output projection (K3o) on device buffers, launched
+ * as forward_rows launches it: out = attention(qkv, mask) Wo^T + bo + resid, as heads / hg
+ * planes [heads/hg][rows][H] (plane g holds head group g's share, plane 0 also bias +
+ * residual); acc != 0: the two planes added into ONE plane, zeroed here first (heads / hg
+ * == 2).  qkv [B*L][3H], Wo [H][H] and resid [B*L][H] are row-major; the hook builds Wo's
+ * frag16 image and, for qf != 0, the frag16 image of qkv with V^T blocks (L % 16 == 0).
+ * cls_only != 0: query 0 of each sequence only, rows = B compact output rows (else rows =
+ * B * L).  hg 4 or 6, dividing heads; L <= 64.  Allocates its operand images: synchronous. */
+int mq_debug_attn_oproj(const float* qkv, const int* mask, int B, int L, int H, int heads, float scale,
+                        const float* Wo, const float* bo, const float* resid, int cls_only, int hg, int qf,
+                        int acc, float* out, void* stream);
 
 /* The int8 screen (K9q) alone for one host query: its kc candidates (screen scores
  * desc, ids; slots past the survivors hold (tau, -1)) and the int8 shadow's statistics

@@ -2732,6 +2732,22 @@ int launch_graph(mq_encoder* e, int B, int L, hipStream_t s) {
   return MQ_OK;
 }
 
+// mq_debug_attn_oproj's QF operand: the image of a row-major qkv [rows][3H] that the QKV
+// launch writes with FL_O | FL_OT - frag16, the V blocks (columns from 2H) transposed
+// within their 16 x 16 block.  One element per thread.
+__global__ __launch_bounds__(256) void frag16_qkv_image_kernel(const float* __restrict__ qkv, int rows, int H,
+                                                               float* __restrict__ img) {
+  const int ld = 3 * H;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)rows * ld) return;
+  const int64_t row = idx / ld;
+  const int col = (int)(idx - row * ld);
+  const bool vt = col >= 2 * H;
+  const int64_t irow = vt ? ((row & ~(int64_t)15) | (col & 15)) : row;
+  const int icol = vt ? ((col & ~15) | (int)(row & 15)) : col;
+  img[frag16_offset(irow, icol, ld)] = qkv[idx];
+}
+
 }  // namespace
 
 extern "C" {
@@ -2885,6 +2901,78 @@ int mq_debug_gemm_f32(const float* A, const float* W, const float* bias, const f
     default: launch_gemm_tile<EPI_RESID>(g, tile, cus, s); break;
   }
   MQ_HIP(hipGetLastError());
+  return MQ_OK;
+}
+
+int mq_debug_attention(const float* qkv, const int* mask, int B, int L, int H, int heads, float scale,
+                       int variant, float* ctx, void* stream) {
+  clear_error();
+  MQ_CHECK_ARG(qkv && mask && ctx, "NULL buffer");
+  MQ_CHECK_ARG(B > 0 && L > 0 && heads > 0 && H == heads * kDh, "bad shape B=%d L=%d H=%d heads=%d", B, L, H, heads);
+  hipStream_t s = (hipStream_t)stream;
+  const int qt = (L + 31) / 32;
+  const dim3 grid(B * heads * qt);
+  switch (variant) {
+    case -1: launch_attention(B, L, heads, qt, H, scale, qkv, mask, ctx, s); break;
+    case 1: hipLaunchKernelGGL(attention_kernel<1>, grid, dim3(64), 0, s, qkv, mask, L, H, heads, qt, scale, ctx); break;
+    case 2: hipLaunchKernelGGL(attention_kernel<2>, grid, dim3(128), 0, s, qkv, mask, L, H, heads, qt, scale, ctx); break;
+    case 4: hipLaunchKernelGGL(attention_kernel<4>, grid, dim3(256), 0, s, qkv, mask, L, H, heads, qt, scale, ctx); break;
+    case 8: hipLaunchKernelGGL(attention_kernel<8>, grid, dim3(512), 0, s, qkv, mask, L, H, heads, qt, scale, ctx); break;
+    case 12:  // one wave per head: the dispatcher's condition on the shape
+      MQ_CHECK_ARG(heads == 12 && L <= 32, "variant 12 needs heads == 12 and L <= 32 (heads %d, L %d)", heads, L);
+      hipLaunchKernelGGL((attention_kernel<1, 12>), dim3(B * qt), dim3(768), 0, s, qkv, mask, L, H, heads, qt, scale,
+                         ctx);
+      break;
+    case 16:
+      MQ_CHECK_ARG(L <= 64, "variant 16 (attention_rows_kernel) needs L <= 64 (got %d)", L);
+      hipLaunchKernelGGL(attention_rows_kernel, grid, dim3(512), 0, s, qkv, mask, L, H, heads, qt, scale, ctx);
+      break;
+    default: MQ_FAIL(MQ_EINVAL, "bad attention variant %d", variant);
+  }
+  MQ_HIP(hipGetLastError());
+  return MQ_OK;
+}
+
+int mq_debug_attn_oproj(const float* qkv, const int* mask, int B, int L, int H, int heads, float scale,
+                        const float* Wo, const float* bo, const float* resid, int cls_only, int hg, int qf,
+                        int acc, float* out, void* stream) {
+  clear_error();
+  MQ_CHECK_ARG(qkv && mask && Wo && bo && resid && out, "NULL buffer");
+  MQ_CHECK_ARG(B > 0 && L > 0 && heads > 0 && H == heads * kDh, "bad shape B=%d L=%d H=%d heads=%d", B, L, H, heads);
+  MQ_CHECK_ARG((hg == 4 || hg == 6) && heads % hg == 0, "hg must be 4 or 6 and divide heads (hg %d, heads %d)", hg,
+               heads);
+  MQ_CHECK_ARG(L <= 64, "the fused kernel holds L <= 64 keys (got %d)", L);
+  MQ_CHECK_ARG(!qf || L % 16 == 0, "qf needs L %% 16 == 0 (got %d)", L);
+  const int planes = heads / hg;
+  MQ_CHECK_ARG(!acc || planes == 2, "acc needs two head groups (got %d)", planes);
+  hipStream_t s = (hipStream_t)stream;
+  const int M = B * L, rows = cls_only ? B : M;
+  float* scratch = nullptr;  // Wo's frag16 image, then (qf) the qkv image
+  const size_t wo_floats = (size_t)H * H, qkv_floats = qf ? (size_t)M * 3 * H : 0;
+  if (hipMalloc((void**)&scratch, (wo_floats + qkv_floats) * 4) != hipSuccess)
+    MQ_FAIL(MQ_ENOMEM, "operand image allocation failed");
+  hipLaunchKernelGGL(frag16_image_kernel, dim3((unsigned)((wo_floats / 4 + 255) / 256)), dim3(256), 0, s, Wo, H, H,
+                     reinterpret_cast<floatx4*>(scratch));
+  const float* qkv_in = qkv;
+  if (qf) {
+    float* img = scratch + wo_floats;
+    hipLaunchKernelGGL(frag16_qkv_image_kernel, dim3((unsigned)((qkv_floats + 255) / 256)), dim3(256), 0, s, qkv, M,
+                       H, img);
+    qkv_in = img;
+  }
+  hipError_t err = hipSuccess;
+  if (acc) err = hipMemsetAsync(out, 0, (size_t)rows * H * 4, s);
+  if (err == hipSuccess) {  // rps, qtiles, ldr and the grid as forward_rows passes them
+    const int rps = cls_only ? 1 : L, qtiles = (rps + 15) / 16;
+    const dim3 grid(H / kOpCols, B * qtiles, planes);
+    launch_attn_oproj(hg, qf != 0, acc != 0, (L + 15) / 16, grid, s, qkv_in, mask, L, H, rps, qtiles, scale, scratch,
+                      bo, resid, cls_only ? L * H : H, out, (int64_t)rows * H, 0);
+    err = hipGetLastError();
+  }
+  const hipError_t serr = hipStreamSynchronize(s);
+  (void)hipFree(scratch);
+  if (err == hipSuccess) err = serr;
+  if (err != hipSuccess) MQ_FAIL(MQ_EHIP, "fused attention + output projection failed: %s", hipGetErrorString(err));
   return MQ_OK;
 }
 

@@ -117,7 +117,9 @@ SIGNATURES = {
     "mq_debug_gemm_x6p": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "mq_debug_gemm_x6p_ln": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_float, _P]),
     "mq_debug_ln_fold_weight": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
-    "mq_debug_int8_screen": (_I, [_P, _P, _I, _P, _P, _P]),
+    "mq_debug_attention": (_I, [_P, _P, _I, _I, _I, _I, ctypes.c_float, _I, _P, _P]),
+    "mq_debug_attn_oproj": (_I, [_P, _P, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "mq_debug_int8_screen":(_I, [_P, _P, _I, _P, _P, _P]),
 }
 
 _lib = None

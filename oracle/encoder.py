@@ -25,9 +25,12 @@ POOL_CLS, POOL_MEAN = 0, 1
 
 
 class OracleEncoder:
-    def __init__(self, cfg, state_dict):
+    def __init__(self, cfg, state_dict, dtype=torch.float32):
+        """dtype: the precision every op runs in (float32: the oracle; float64: the
+        reference the kernel accuracy tests measure the oracle's own rounding against)."""
         self.cfg = cfg
-        t = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32)
+        self.dtype = dtype
+        t = lambda a: torch.as_tensor(np.asarray(a), dtype=dtype)
         sd = {k: t(v) for k, v in state_dict.items()}
         self.word = sd["embeddings.word_embeddings.weight"]
         self.pos = sd["embeddings.position_embeddings.weight"]
@@ -57,9 +60,16 @@ class OracleEncoder:
             return 0.5 * x * (1.0 + torch.tanh(math.sqrt(2.0 / math.pi) * (x + 0.044715 * x ** 3)))
         return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
 
+    @staticmethod
+    def attention(q, k, v, bias, dh):
+        """q, k, v [B, heads, L, dh], bias [B, 1, 1, L] (0 / -inf per key) -> [B, heads, L, dh]."""
+        s = (q @ k.transpose(-1, -2)) / math.sqrt(dh) + bias
+        p = torch.softmax(s, dim=-1)
+        return p @ v
+
     @torch.no_grad()
     def hidden_states(self, ids, mask):
-        """ids, mask: int arrays [B, L] -> last hidden state [B, L, H] (fp32)."""
+        """ids, mask: int arrays [B, L] -> last hidden state [B, L, H] (self.dtype)."""
         cfg = self.cfg
         ids = torch.as_tensor(np.asarray(ids), dtype=torch.long)
         keep = torch.as_tensor(np.asarray(mask), dtype=torch.bool)
@@ -68,16 +78,14 @@ class OracleEncoder:
         dh = H // nh
         x = self.word[ids] + self.pos[:L].unsqueeze(0) + self.typ[0]
         x = self._ln(x, self.eln)
-        bias = torch.zeros(B, 1, 1, L)
+        bias = torch.zeros(B, 1, 1, L, dtype=self.dtype)
         bias.masked_fill_(~keep[:, None, None, :], float("-inf"))
         for w in self.layers:
             heads = lambda y: y.view(B, L, nh, dh).transpose(1, 2)
             q = heads(x @ w["wq"].T + w["bq"])
             k = heads(x @ w["wk"].T + w["bk"])
             v = heads(x @ w["wv"].T + w["bv"])
-            s = (q @ k.transpose(-1, -2)) / math.sqrt(dh) + bias
-            p = torch.softmax(s, dim=-1)
-            ctx = (p @ v).transpose(1, 2).reshape(B, L, H)
+            ctx = self.attention(q, k, v, bias, dh).transpose(1, 2).reshape(B, L, H)
             x = self._ln(x + ctx @ w["wo"].T + w["bo"], w["ln1"])
             h = self._gelu(x @ w["w1"].T + w["b1"])
             x = self._ln(x + h @ w["w2"].T + w["b2"], w["ln2"])
@@ -87,9 +95,9 @@ class OracleEncoder:
         """-> unit-norm embeddings [B, H] as float32 numpy (CLS or mean pooling)."""
         h = self.hidden_states(ids, mask)
         if self.cfg.pooling == POOL_MEAN:
-            m = torch.as_tensor(np.asarray(mask), dtype=torch.float32).unsqueeze(-1)
+            m = torch.as_tensor(np.asarray(mask), dtype=self.dtype).unsqueeze(-1)
             e = (h * m).sum(1) / m.sum(1).clamp_min(1.0)
         else:
             e = h[:, 0]
         e = e / e.norm(dim=-1, keepdim=True).clamp_min(1e-12)
-        return e.numpy().astype(np.float32)
+        return e.numpy().astype(np.float32 if self.dtype == torch.float32 else np.float64)
