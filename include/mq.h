@@ -197,6 +197,53 @@ int mq_index_search_masked_batch(mq_index* ix, const float* queries, int64_t nq,
                                  float* out_scores, int64_t* out_ids, int io_on_device, void* stream);
 int mq_index_masked_gathers(const mq_index* ix, int64_t* count);
 
+/* Maximal marginal relevance (LangChain's maximal_marginal_relevance, the selection behind
+ * VectorStore.max_marginal_relevance_search): from each query's candidate list pick k rows
+ * greedily, trading similarity to the query against similarity to the rows already picked.
+ * Candidates c_0 .. c_{m-1} in list order, s_i = cand_scores[i] (taken as given: the search's
+ * exact fp32 dot, never recomputed), G[i][j] = the fp32 dot of stored rows cand_ids[i] and
+ * cand_ids[j] (unit-norm already, not renormalised):
+ *   pick 0    = argmax_i s_i
+ *   pick t    = argmax over the unpicked i of MQ_MMR_SCORE(lambda, s_i, red_i),
+ *               red_i = max over the picked p of G[i][p]
+ * Ties go to the lowest list position i (LangChain compares with a strict >).  The score is
+ * fixed fp32 arithmetic, each operation rounded to nearest, never contracted into an FMA:
+ *   score = fsub(fmul(lambda, s), fmul(fsub(1.0f, lambda), red))
+ * written once below as MQ_MMR_SCORE over the caller's rounding primitives (the kernel
+ * passes __fmul_rn / __fsub_rn; a host restatement passes non-contracting float ops).
+ * (mmr_select_kernel, K11: one workgroup per query; the fetch_k x fetch_k Gram matrix on
+ * the exact-f32 MFMA from K-slices of the candidate rows staged through LDS, bitwise
+ * symmetric; then one wave runs the greedy loop with lane i owning candidate i.)
+ * cand_scores [nq, fetch_k] f32 and cand_ids [nq, fetch_k] int64 need not be sorted; an id
+ * outside [0, size) is padding: its row is never read and it is never picked.
+ * out_ids [nq, k] = the picked row ids in selection order, out_scores [nq, k] = their s_i;
+ * with fewer than k valid candidates the rest is (-inf, -1).  All four buffers host
+ * (io_on_device = 0, synchronous) or all device (asynchronous on `stream`).
+ * 1 <= k <= fetch_k <= MQ_MAX_K, lambda finite in [0, 1], nq >= 0.  A query's result does
+ * not depend on the rest of the batch. */
+#define MQ_MMR_SCORE(fmul, fsub, lambda, s, red) \
+  fsub(fmul((lambda), (s)), fmul(fsub(1.0f, (lambda)), (red)))
+int mq_index_mmr_select(mq_index* ix, const float* cand_scores, const int64_t* cand_ids, int64_t nq,
+                        int fetch_k, int k, float lambda, float* out_scores, int64_t* out_ids,
+                        int io_on_device, void* stream);
+/* Search, then select: the top min(fetch_k, size) of each query at the index's current
+ * precision (bits == NULL: mq_index_search; a device mask: the masked search, as
+ * mq_index_search_masked_batch) go into a workspace kept for the index's handle (grown on
+ * demand, never allocated per call; kept under the handle's address for the life of the
+ * process, so mq_index_destroy does not free it and a later handle at that address reuses
+ * it), and mmr_select_kernel runs on them on the same stream: no host round trip beyond the
+ * search's own.  queries [nq, dim], outputs [nq, k] as mq_index_mmr_select; an empty index
+ * returns only padding.
+ * Both MMR calls hold a mutex of the handle's workspace from start to end, so they serialise
+ * with each other on one handle as the other mq_index_* calls do on the index's own mutex.
+ * That mutex is not the index's: the selection reads the row slab (pointer and row count)
+ * as it stood when the call began, so an mq_index_add / _select / _reset / _load on the same
+ * handle must not run concurrently with an MMR call (an add that regrows the slab frees
+ * the rows the kernel reads). */
+int mq_index_search_mmr(mq_index* ix, const float* queries, int64_t nq, int k, int fetch_k,
+                        float lambda, const uint32_t* bits, float* out_scores, int64_t* out_ids,
+                        int io_on_device, void* stream);
+
 /* Persistence: a flat binary slab (header + rows); written files are
  * fsync'ed before the call returns. */
 int mq_index_save(mq_index* ix, const char* path);

@@ -92,6 +92,8 @@ SIGNATURES = {
     "mq_index_search_masked": (_I, [_P, _P, _I, _P, _P, _P, _I, _P]),
     "mq_index_search_masked_batch": (_I, [_P, _P, _I64, _I, _P, _P, _P, _I, _P]),
     "mq_index_masked_gathers": (_I, [_P, ctypes.POINTER(_I64)]),
+    "mq_index_mmr_select": (_I, [_P, _P, _P, _I64, _I, _I, ctypes.c_float, _P, _P, _I, _P]),
+    "mq_index_search_mmr": (_I, [_P, _P, _I64, _I, _I, ctypes.c_float, _P, _P, _P, _I, _P]),
     "mq_topk_merge_host": (_I, [_P, _P, _I, _I64, _I, _I, _P, _P]),
     "mq_topk_merge_device": (_I, [_P, _P, _I, _I64, _I, _I, _P, _P, _P]),
     "mq_encoder_create": (_I, [_I, ctypes.POINTER(BertConfigC), _PP]),

@@ -57,11 +57,19 @@ except Exception:
             return cls.from_texts(texts, embedding, metadatas=metadatas, **kwargs)
 
         def as_retriever(self, **kwargs):
-            k = kwargs.get("search_kwargs", {}).get("k", 4)
+            search_kwargs = kwargs.get("search_kwargs", {})
+            k = search_kwargs.get("k", 4)
             store = self
+            # search_type="mmr" (LangChain's VectorStoreRetriever): k, fetch_k, lambda_mult and
+            # filter of search_kwargs go to max_marginal_relevance_search
+            mmr = kwargs.get("search_type") == "mmr"
+            mmr_kwargs = {a: search_kwargs[a] for a in ("k", "fetch_k", "lambda_mult", "filter")
+                          if a in search_kwargs}
 
             class _Retriever:
                 def invoke(self, query, **_):
+                    if mmr:
+                        return store.max_marginal_relevance_search(query, **mmr_kwargs)
                     return store.similarity_search(query, k=k)
 
                 get_relevant_documents = invoke

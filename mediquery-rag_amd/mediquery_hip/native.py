@@ -181,6 +181,45 @@ class FlatIndex:
                       _lib.ptr(scores), _lib.ptr(ids), 0, _lib.stream_handle(None))
         return scores, ids
 
+    def mmr_select(self, cand_scores, cand_ids, k, lambda_mult=0.5):
+        """Maximal-marginal-relevance selection (K11, mq_index_mmr_select) over each query's
+        candidate list: cand_scores [nq, fetch_k] f32 (each candidate's cosine to the query,
+        taken as given), cand_ids [nq, fetch_k] int64 row ids (any order; an id outside
+        [0, n) is padding).  -> (scores [nq, k], ids [nq, k]) in selection order, padded
+        with (-inf, -1) when fewer than k candidates are valid."""
+        s = np.ascontiguousarray(cand_scores, dtype=np.float32)
+        i = np.ascontiguousarray(cand_ids, dtype=np.int64)
+        s = s.reshape(1, -1) if s.ndim == 1 else s
+        i = i.reshape(s.shape)
+        scores = np.empty((s.shape[0], k), dtype=np.float32)
+        ids = np.empty((s.shape[0], k), dtype=np.int64)
+        with _lib.device_scope(self.device):
+            _lib.call("mq_index_mmr_select", self._h, _lib.ptr(s), _lib.ptr(i), s.shape[0], s.shape[1], k,
+                      float(lambda_mult), _lib.ptr(scores), _lib.ptr(ids), 0, _lib.stream_handle(None))
+        return scores, ids
+
+    def mmr_select_device(self, cand_scores, cand_ids, k, lambda_mult, out_scores, out_ids, stream=None):
+        """mmr_select on torch device tensors (cand_* [nq, fetch_k], out_* [nq, k]),
+        asynchronous on the given (or current) torch stream."""
+        _lib.call("mq_index_mmr_select", self._h, _lib.ptr(cand_scores), _lib.ptr(cand_ids),
+                  cand_scores.shape[0], cand_scores.shape[1], k, float(lambda_mult), _lib.ptr(out_scores),
+                  _lib.ptr(out_ids), 1, _lib.stream_handle(stream))
+
+    def search_mmr(self, queries, k, fetch_k, lambda_mult=0.5, bits=None):
+        """Top-fetch_k search at the index's precision, then the MMR selection of k of them on
+        the device (mq_index_search_mmr): one call, nothing row-sized leaves HBM.  `bits`: a
+        row mask as for search_masked (None = every row).  -> (scores [nq, k], ids [nq, k])
+        in selection order, scores = cosine to the query."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        if bits is not None:
+            self._check_bits(bits)
+        scores = np.empty((q.shape[0], k), dtype=np.float32)
+        ids = np.empty((q.shape[0], k), dtype=np.int64)
+        with _lib.device_scope(self.device):
+            _lib.call("mq_index_search_mmr", self._h, _lib.ptr(q), q.shape[0], k, fetch_k, float(lambda_mult),
+                      _lib.ptr(bits), _lib.ptr(scores), _lib.ptr(ids), 0, _lib.stream_handle(None))
+        return scores, ids
+
     @property
     def masked_gathers(self):
         """Masked searches the int8 screen did not certify (answered from gathered rows)."""

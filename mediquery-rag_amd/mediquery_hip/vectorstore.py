@@ -682,6 +682,55 @@ class HipChroma(VectorStoreBase):
         _, ids = self._index.search(q, kk)
         return [[self._doc(int(r)) for r in row if r >= 0] for row in ids]
 
+    # ---- maximal marginal relevance --------------------------------------------------------
+    def _mmr_rows(self, q, k, fetch_k, lambda_mult, filter=None):
+        """-> per query the rows LangChain's maximal_marginal_relevance picks from the top
+        fetch_k, in selection order: one search + one selection launch on the device
+        (mq_index_search_mmr).  fetch_k is clipped to the candidate rows (the store's, or the
+        filter's) and must then fit the device top-k; k > fetch_k returns fetch_k rows."""
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self._dim or 1)
+        n = 0 if self._index is None else len(self._index)
+        if n == 0 or k <= 0 or fetch_k <= 0 or not len(q):
+            return [[] for _ in range(len(q))]
+        bits = None
+        if filter:
+            # the filter's row count decides between raising and clipping, as in _search_rows
+            if fetch_k > _lib.MQ_MAX_K:
+                fetch_k = _check_k(fetch_k, int(self._cols.mask(filter).sum()))
+                if fetch_k == 0:
+                    return [[] for _ in range(len(q))]
+            fetch_k = min(int(fetch_k), n)
+            bits = self._cols.dmask(filter, self._device)
+        else:
+            fetch_k = _check_k(fetch_k, n)
+        _, ids = self._index.search_mmr(q, min(int(k), fetch_k), fetch_k, float(lambda_mult), bits)
+        return [[int(r) for r in row if r >= 0] for row in ids]
+
+    def max_marginal_relevance_search_by_vector(self, embedding, k=DEFAULT_K, fetch_k=20, lambda_mult=0.5,
+                                                filter=None, **kwargs):
+        """LangChain's MMR search: the k of the fetch_k most similar rows that trade similarity
+        to the query (weight lambda_mult) against similarity to the rows already picked
+        (weight 1 - lambda_mult), as Documents in selection order."""
+        return [self._doc(r) for r in self._mmr_rows(embedding, k, fetch_k, lambda_mult, filter)[0]]
+
+    def max_marginal_relevance_search(self, query, k=DEFAULT_K, fetch_k=20, lambda_mult=0.5, filter=None,
+                                      **kwargs):
+        if (self._index is None or len(self._index) == 0) or k <= 0:
+            return []
+        return self.max_marginal_relevance_search_by_vector(self._embed_query(query), k, fetch_k, lambda_mult,
+                                                            filter)
+
+    def max_marginal_relevance_search_batch(self, queries, k=DEFAULT_K, fetch_k=20, lambda_mult=0.5, filter=None):
+        """Many queries: one encoder batch, one device search and one selection launch."""
+        n = 0 if self._index is None else len(self._index)
+        if n == 0 or not queries or k <= 0:
+            return [[] for _ in queries]
+        if hasattr(self._embedding_function, "embed_array"):
+            q = self._embedding_function.embed_array(list(queries))
+        else:
+            q = np.asarray(self._embedding_function.embed_documents(list(queries)), np.float32)
+        return [[self._doc(r) for r in rows] for rows in self._mmr_rows(q, k, fetch_k, lambda_mult, filter)]
+
     def _select_relevance_score_fn(self):
         if self.override_relevance_score_fn:
             return self.override_relevance_score_fn
