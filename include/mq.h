@@ -196,6 +196,36 @@ int mq_index_search_masked(mq_index* ix, const float* query, int k, const uint32
 int mq_index_search_masked_batch(mq_index* ix, const float* queries, int64_t nq, int k, const uint32_t* bits,
                                  float* out_scores, int64_t* out_ids, int io_on_device, void* stream);
 int mq_index_masked_gathers(const mq_index* ix, int64_t* count);
+/* Document-text conditions (Chroma's `where_document={"$contains": s}` / `$not_contains` on
+ * `similarity_search*`, `max_marginal_relevance_search*` and `get` of the LangChain Chroma
+ * surface, which the store replaces: src/medical_engine.py:52) as a row mask for the masked
+ * searches above: bits (mode)= contains(r) ^ negate for rows [0, n), where contains(r) = the
+ * pattern's bytes occur in row r's bytes (a byte-substring match: on UTF-8 text it equals the
+ * substring match of the decoded strings; a match never spans two rows).  mode MQ_MASK_SET /
+ * AND / OR as mq_mask_eval; the bits past n in the last word come out 0 under SET and AND
+ * (also with negate) and unchanged under OR; n == 0 is a no-op.
+ *   text     device, the rows' UTF-8 bytes concatenated, 16-byte aligned (any hipMalloc'ed or
+ *            torch buffer's start); only [0, text_bytes) is read, no padding behind it is
+ *            needed.  May be NULL when text_bytes == 0.
+ *   offsets  device int64 [n + 1], non-decreasing, offsets[0] == 0, offsets[n] == text_bytes;
+ *            row r is text[offsets[r], offsets[r + 1]) (zero-length rows allowed).  The kernel
+ *            trusts them, but writes no bit outside rows [0, n) whatever they hold.
+ *   pattern  HOST pointer, pattern_len in [1, MQ_CONTAINS_MAX_BYTES] bytes, passed to the
+ *            kernel by value (no host-to-device copy per condition, as mq_mask_eval_bits).
+ *   negate   0 or 1.
+ *   scratch  device, ceil(n / 32) words the call overwrites (the hit mask the scan ORs into
+ *            before negate and mode are applied; the caller provides it so that the call
+ *            allocates and frees no device memory); not bits.
+ * The scan (contains_scan_kernel, K12) gives each workgroup one span of
+ * MQ_CONTAINS_SPAN_BYTES text bytes (+ a halo of pattern_len - 1), 64-bit byte addressing
+ * throughout.  Asynchronous on `stream`; launches on the GPU the buffers live on.  The argument
+ * checks (sizes, pattern_len, mode, negate, NULL pointers with n > 0, alignment) come before
+ * any HIP call. */
+#define MQ_CONTAINS_MAX_BYTES 256
+#define MQ_CONTAINS_SPAN_BYTES 16384
+int mq_mask_contains(const uint8_t* text, int64_t text_bytes, const int64_t* offsets, int64_t n,
+                     const uint8_t* pattern, int pattern_len, int negate, uint32_t* bits, int mode,
+                     uint32_t* scratch, void* stream);
 
 /* Maximal marginal relevance (LangChain's maximal_marginal_relevance, the selection behind
  * VectorStore.max_marginal_relevance_search): from each query's candidate list pick k rows

@@ -60,17 +60,19 @@ except Exception:
             search_kwargs = kwargs.get("search_kwargs", {})
             k = search_kwargs.get("k", 4)
             store = self
-            # search_type="mmr" (LangChain's VectorStoreRetriever): k, fetch_k, lambda_mult and
-            # filter of search_kwargs go to max_marginal_relevance_search
+            # search_type="mmr" (LangChain's VectorStoreRetriever): k, fetch_k, lambda_mult,
+            # filter and where_document of search_kwargs go to max_marginal_relevance_search;
+            # the plain type passes filter and where_document on too, as LangChain's does
             mmr = kwargs.get("search_type") == "mmr"
-            mmr_kwargs = {a: search_kwargs[a] for a in ("k", "fetch_k", "lambda_mult", "filter")
+            mmr_kwargs = {a: search_kwargs[a] for a in ("k", "fetch_k", "lambda_mult", "filter", "where_document")
                           if a in search_kwargs}
+            sim_kwargs = {a: search_kwargs[a] for a in ("filter", "where_document") if a in search_kwargs}
 
             class _Retriever:
                 def invoke(self, query, **_):
                     if mmr:
                         return store.max_marginal_relevance_search(query, **mmr_kwargs)
-                    return store.similarity_search(query, k=k)
+                    return store.similarity_search(query, k=k, **sim_kwargs)
 
                 get_relevant_documents = invoke
 

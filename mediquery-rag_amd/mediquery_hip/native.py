@@ -388,6 +388,37 @@ def mask_eval_bits(codes, lut, bits, mode, stream=None):
                   mode, _lib.stream_handle(stream))
 
 
+def mask_contains(text, offsets, pattern, bits, mode, negate=False, stream=None, scratch=None):
+    """bits (mode)= (pattern occurs in row r) ^ negate on the device (include/mq.h
+    mq_mask_contains): text uint8 [text_bytes] = the rows' UTF-8 bytes concatenated, offsets
+    int64 [n + 1] (row r = text[offsets[r]:offsets[r + 1]]), pattern 1..MQ_CONTAINS_MAX_BYTES
+    host bytes, bits int32 [ceil(n / 32)] (torch, one device; the launch runs there, on
+    `stream` or that device's current stream).  scratch: ceil(n / 32) words the call
+    overwrites (None: a torch.empty of that size)."""
+    import torch
+    if not (getattr(text, "is_cuda", False) and text.dtype == torch.uint8 and text.is_contiguous()
+            and text.dim() == 1):
+        raise ValueError("text must be a contiguous 1-d uint8 device tensor")
+    if text.numel() and text.data_ptr() % 16:
+        raise ValueError("text must start at a 16-byte aligned address")
+    if not (getattr(offsets, "is_cuda", False) and offsets.dtype == torch.int64 and offsets.is_contiguous()
+            and offsets.numel() >= 1 and offsets.device == text.device):
+        raise ValueError("offsets must be a contiguous int64 tensor of n + 1 elements on the text's device")
+    n = offsets.numel() - 1
+    check_mask_words(bits, n, text.device.index)
+    if not isinstance(pattern, (bytes, bytearray)) or not 1 <= len(pattern) <= _lib.MQ_CONTAINS_MAX_BYTES:
+        raise ValueError("pattern must be 1..%d bytes" % _lib.MQ_CONTAINS_MAX_BYTES)
+    with _lib.device_scope(text.device.index):
+        if scratch is None:
+            scratch = torch.empty(max(1, (n + 31) // 32), dtype=torch.int32, device=text.device)
+        check_mask_words(scratch, n, text.device.index)
+        if scratch.data_ptr() == bits.data_ptr():
+            raise ValueError("scratch must not be bits")
+        _lib.call("mq_mask_contains", _lib.ptr(text), text.numel(), _lib.ptr(offsets), n, bytes(pattern),
+                  len(pattern), int(bool(negate)), _lib.ptr(bits), mode, _lib.ptr(scratch),
+                  _lib.stream_handle(stream))
+
+
 def mask_combine(dst, src, mode, stream=None):
     """dst (mode)= src (None: all ones; MQ_MASK_CLEAR: zeros) on the device."""
     check_mask_words(dst, 0)

@@ -15,7 +15,10 @@ unit-norm embeddings is 2 - 2*cos; `similarity_search` returns documents by asce
 distance, ties broken by insertion order.  k > N returns N documents; an empty store
 returns [].  The device top-k holds at most MQ_MAX_K (64) results: a search whose result
 count min(k, candidates) exceeds it raises instead of truncating.  Errors raise (the
-reference's retrieve_node does not catch either).
+reference's retrieve_node does not catch either).  Chroma's two query filters both run as
+device row masks: `filter` / `where` over metadata code columns (`_MetaColumns`), and
+`where_document` ($contains / $not_contains / $and / $or on the text) over a device mirror of
+the documents (`_TextMirror`, built at its first use; `_match_document` is the definition).
 
 Persistence: `mq_<collection>.json` (ids, documents, metadatas, and the name of the slab
 file) is the base commit point; a full write (the first write, `delete`, an upsert that
@@ -42,7 +45,7 @@ import numpy as np
 
 from . import _lib
 from .compat import Document, VectorStoreBase
-from .native import FlatIndex, mask_combine, mask_eval, mask_eval_bits
+from .native import FlatIndex, mask_combine, mask_contains, mask_eval, mask_eval_bits
 
 DEFAULT_K = 4  # LangChain VectorStore.similarity_search default; the reference passes k=5
 
@@ -86,6 +89,55 @@ def _match(meta, where):
             elif v != cond:
                 return False
     return True
+
+
+_DOC_LEAVES = ("$contains", "$not_contains")
+
+
+def _check_where_document(clause, path="where_document"):
+    """Validate a Chroma `where_document` clause: a dict with exactly one key, {"$contains": s}
+    / {"$not_contains": s} (s a non-empty str of at most MQ_CONTAINS_MAX_BYTES UTF-8 bytes) or
+    {"$and" / "$or": [clause, ...]} (a non-empty list, nesting allowed).  Anything else -
+    Chroma's $regex / $not_regex included - raises ValueError naming the offending part.  The
+    one validation of the host (`_match_document`) and device (`HipChroma._doc_bits`) paths."""
+    if not isinstance(clause, dict) or len(clause) != 1:
+        raise ValueError("%s must be a dict with exactly one key, got %r" % (path, clause))
+    op, x = next(iter(clause.items()))
+    if op in _DOC_LEAVES:
+        if not isinstance(x, str) or not x:
+            raise ValueError("%s: the operand of %s must be a non-empty str, got %r" % (path, op, x))
+        nb = len(x.encode("utf-8"))
+        if nb > _lib.MQ_CONTAINS_MAX_BYTES:
+            raise ValueError("%s: the operand of %s is %d UTF-8 bytes, the limit is MQ_CONTAINS_MAX_BYTES=%d"
+                             % (path, op, nb, _lib.MQ_CONTAINS_MAX_BYTES))
+    elif op in ("$and", "$or"):
+        if not isinstance(x, (list, tuple)) or not x:
+            raise ValueError("%s: %s takes a non-empty list of clauses, got %r" % (path, op, x))
+        for j, c in enumerate(x):
+            _check_where_document(c, "%s[%r][%d]" % (path, op, j))
+    else:
+        raise ValueError("%s: unsupported where_document operator %r (supported: $contains, "
+                         "$not_contains, $and, $or)" % (path, op))
+    return clause
+
+
+def _eval_where_document(text, clause):
+    op, x = next(iter(clause.items()))
+    if op == "$contains":
+        return x in text
+    if op == "$not_contains":
+        return x not in text
+    if op == "$and":
+        return all(_eval_where_document(text, c) for c in x)
+    return any(_eval_where_document(text, c) for c in x)
+
+
+def _match_document(text, where_document):
+    """Chroma-style document filter on one row's page_content, row by row in plain Python (as
+    `_match` is for metadata): case-sensitive substring match, no normalisation, no
+    tokenisation.  The device path (mq_mask_contains) matches the UTF-8 bytes instead; UTF-8
+    is self-synchronising, so the two agree for every pair of str."""
+    return _eval_where_document(text, _check_where_document(where_document))
 
 
 _MISSING = object()
@@ -262,6 +314,57 @@ class _MetaColumns:
         return out
 
 
+class _TextMirror:
+    """Device mirror of the documents for `where_document`: the rows' UTF-8 bytes concatenated
+    (`blob`, uint8) and their int64 offsets [n + 1], both with capacity doubling, plus the
+    scratch hit mask mq_mask_contains wants.  Built at the first `where_document` use; a plain
+    append uploads only the new bytes and offsets; `epoch` (the store bumps its own on every
+    delete, so also on a replacing upsert) tells when the rows were renumbered and the mirror
+    must be rebuilt.  Costs the corpus's UTF-8 bytes + 8 bytes a row of HBM."""
+
+    def __init__(self, device, epoch):
+        import torch
+        self.dev = torch.device("cuda", device)
+        self.epoch = epoch
+        self.version = -1  # the store's _version the mirror is in step with
+        self.n = 0
+        self.nbytes = 0
+        self.blob = torch.empty(0, dtype=torch.uint8, device=self.dev)
+        self.offs = torch.zeros(1, dtype=torch.int64, device=self.dev)
+        self.scratch = torch.empty(1, dtype=torch.int32, device=self.dev)
+
+    @staticmethod
+    def _grown(buf, used, need):
+        import torch
+        if buf.numel() >= need:
+            return buf
+        out = torch.empty(max(need, 2 * buf.numel()), dtype=buf.dtype, device=buf.device)
+        out[:used] = buf[:used]
+        return out
+
+    def extend(self, texts):
+        """Append rows `texts` (the store's rows n .. n + len(texts))."""
+        import torch
+        if not texts:
+            return
+        enc = [t.encode("utf-8") for t in texts]
+        ends = self.nbytes + np.cumsum(np.fromiter(map(len, enc), np.int64, len(enc)))
+        new = b"".join(enc)
+        self.blob = self._grown(self.blob, self.nbytes, self.nbytes + len(new))
+        self.offs = self._grown(self.offs, self.n + 1, self.n + 1 + len(enc))
+        if new:
+            self.blob[self.nbytes:self.nbytes + len(new)] = torch.frombuffer(bytearray(new), dtype=torch.uint8).to(self.dev)
+        self.offs[self.n + 1:self.n + 1 + len(enc)] = torch.from_numpy(ends).to(self.dev)
+        self.n += len(enc)
+        self.nbytes += len(new)
+        self.scratch = self._grown(self.scratch, 0, (self.n + 31) // 32)
+
+    def contains(self, pattern, bits, mode, negate):
+        """bits (mode)= (row contains pattern) ^ negate over the mirror's rows."""
+        mask_contains(self.blob[:self.nbytes], self.offs[:self.n + 1], pattern, bits, mode, negate,
+                      scratch=self.scratch)
+
+
 class _IdRows:
     """id -> current row in O(1), kept across deletes without rebuilding a dict of every id:
     each id gets a stable slot when it is added (`slot`, a dict), and two int64 arrays map
@@ -378,6 +481,9 @@ class HipChroma(VectorStoreBase):
         self._id_row = _IdRows()       # id -> row (upsert / delete / get by id in O(1))
         self._cols = _MetaColumns()    # metadata column-wise, for vectorised filters
         self._version = 0              # bumped by every write
+        self._text_epoch = 0           # bumped when rows are renumbered (delete, replacing upsert)
+        self._doc_mirror = None        # _TextMirror, built at the first where_document use
+        self._doc_cache = None         # ((clause JSON, _version), device mask) of the last clause
         self._index = None
         self._dim = dim
         self._slab_name = None
@@ -605,17 +711,22 @@ class HipChroma(VectorStoreBase):
         self._cols.compact(keep)
         self._id_row.compact(keep, gone)
         self._version += 1
+        self._text_epoch += 1
         if _persist:
             self._persist()
         return True
 
-    def get(self, ids=None, where=None, limit=None, offset=None, include=None, **kwargs):
+    def get(self, ids=None, where=None, limit=None, offset=None, include=None, where_document=None, **kwargs):
+        if where_document is not None:
+            _check_where_document(where_document)
         rows = np.arange(len(self._ids))
         if ids is not None:
             want = [ids] if isinstance(ids, str) else ids
             rows = np.array(sorted({self._id_row.row(i) for i in want if i in self._id_row}), np.int64)
         if where:
             rows = rows[self._cols.mask(where)[rows]]
+        if where_document is not None and len(rows):
+            rows = rows[self._mask_rows(self._doc_bits(where_document))[rows]]
         rows = rows.tolist()[offset or 0:]
         if limit is not None:
             rows = rows[:limit]
@@ -623,47 +734,128 @@ class HipChroma(VectorStoreBase):
                 "metadatas": [self._metas[r] for r in rows]}
 
     # ---- search -------------------------------------------------------------------------
-    def _search_rows(self, vec, k, filter=None):
+    def _doc_apply(self, clause, bits, mode):
+        """bits (mode)= clause on the device: a leaf is one mq_mask_contains ($not_contains:
+        negate); $and / $or chain ANDs / ORs, through a scratch mask when `mode` is not theirs."""
+        import torch
+        op, x = next(iter(clause.items()))
+        if op in _DOC_LEAVES:
+            self._doc_mirror.contains(x.encode("utf-8"), bits, mode, op == "$not_contains")
+            return
+        own = _lib.MQ_MASK_AND if op == "$and" else _lib.MQ_MASK_OR
+        if mode == own:
+            for c in x:
+                self._doc_apply(c, bits, own)
+            return
+        tmp = torch.empty_like(bits)
+        self._doc_apply(x[0], tmp, _lib.MQ_MASK_SET)
+        for c in x[1:]:
+            self._doc_apply(c, tmp, own)
+        mask_combine(bits, tmp, mode)
+
+    def _doc_bits(self, where_document):
+        """Device row mask of a (validated) where_document clause over the current rows.  The
+        mask of the last clause is kept, keyed by the clause's canonical JSON and _version: a
+        retriever with fixed search_kwargs scans the text once, not once per query, and any
+        write misses.  The text mirror is built here on first use, extended after plain appends
+        and rebuilt after a delete.  The returned tensor is shared: callers only read it."""
+        import torch
+        key = (json.dumps(where_document, sort_keys=True, ensure_ascii=False), self._version)
+        if self._doc_cache is not None and self._doc_cache[0] == key:
+            return self._doc_cache[1]
+        self._doc_cache = None
+        mir = self._doc_mirror
+        if mir is None or mir.epoch != self._text_epoch:
+            self._doc_mirror = None  # release the old mirror before building the new one
+            mir = self._doc_mirror = _TextMirror(self._device, self._text_epoch)
+        if mir.version != self._version:
+            mir.extend(self._texts[mir.n:])
+            mir.version = self._version
+        with _lib.device_scope(self._device):
+            bits = torch.empty(max(1, (mir.n + 31) // 32), dtype=torch.int32, device=mir.dev)
+            self._doc_apply(where_document, bits, _lib.MQ_MASK_SET)
+        self._doc_cache = (key, bits)
+        return bits
+
+    def _mask_rows(self, bits):
+        """A device row mask read back as bool [n rows]."""
+        n = len(self._ids)
+        return np.unpackbits(bits.cpu().numpy().view(np.uint8), bitorder="little")[:n].astype(bool)
+
+    def _admit(self, k, filter, where_document):
+        """-> (k, bits): the device row mask of `filter` and `where_document` together (a row is
+        admitted when both admit it; at least one is given) and k clipped for it as the filtered
+        search clips it: past MQ_MAX_K the admitted-row count decides between raising and
+        returning them all (k = 0: no row is admitted, bits None)."""
+        if where_document is None:
+            if k > _lib.MQ_MAX_K:
+                k = _check_k(k, int(self._cols.mask(filter).sum()))
+                if k == 0:
+                    return 0, None
+            return k, self._cols.dmask(filter, self._device)
+        bits = self._doc_bits(where_document)
+        if filter:
+            both = self._cols.dmask(filter, self._device)
+            mask_combine(both, bits, _lib.MQ_MASK_AND)
+            bits = both
+        if k > _lib.MQ_MAX_K:  # the count comes from the combined mask
+            k = _check_k(k, int(self._mask_rows(bits).sum()))
+            if k == 0:
+                return 0, None
+        return k, bits
+
+    def _search_rows(self, vec, k, filter=None, where_document=None):
         """-> list of (row, cosine) for one query vector, best first."""
+        if where_document is not None:
+            _check_where_document(where_document)
         n = 0 if self._index is None else len(self._index)
         if n == 0 or k <= 0:
             return []
         q = np.ascontiguousarray(vec, dtype=np.float32).reshape(1, -1)
-        if not filter:
+        if not filter and where_document is None:
             kk = _check_k(k, n)
             s, i = self._index.search(q, kk)
             return [(int(r), float(c)) for r, c in zip(i[0], s[0]) if r >= 0]
         # exact filtered search on the device: the where-mask built from the device codes
         # (mq_mask_eval), then the masked search (int8 certified screen with the mask, or
         # the allowed rows gathered on the device); nothing row-sized crosses PCIe
-        if k > _lib.MQ_MAX_K:  # the result count decides between raising and returning all
-            k = _check_k(k, int(self._cols.mask(filter).sum()))
-            if k == 0:
-                return []
-        bits = self._cols.dmask(filter, self._device)
+        # (a where_document clause: mq_mask_contains over the device text mirror, ANDed in)
+        k, bits = self._admit(k, filter, where_document)  # the result count decides between
+        if k == 0:                                        # raising and returning all
+            return []
         s, i = self._index.search_masked(q, int(k), bits)
         return [(int(r), float(c)) for r, c in zip(i[0], s[0]) if r >= 0]
 
-    def similarity_search_by_vector_with_score(self, embedding, k=DEFAULT_K, filter=None, **kwargs):
-        return [(self._doc(r), max(0.0, 2.0 - 2.0 * c)) for r, c in self._search_rows(embedding, k, filter)]
+    def similarity_search_by_vector_with_score(self, embedding, k=DEFAULT_K, filter=None, where_document=None,
+                                               **kwargs):
+        return [(self._doc(r), max(0.0, 2.0 - 2.0 * c))
+                for r, c in self._search_rows(embedding, k, filter, where_document)]
 
-    def similarity_search_by_vector(self, embedding, k=DEFAULT_K, filter=None, **kwargs):
-        return [d for d, _ in self.similarity_search_by_vector_with_score(embedding, k, filter)]
+    def similarity_search_by_vector(self, embedding, k=DEFAULT_K, filter=None, where_document=None, **kwargs):
+        return [d for d, _ in self.similarity_search_by_vector_with_score(embedding, k, filter, where_document)]
 
-    def similarity_search_with_score(self, query, k=DEFAULT_K, filter=None, **kwargs):
-        return self.similarity_search_by_vector_with_score(self._embed_query(query), k, filter)
+    def similarity_search_with_score(self, query, k=DEFAULT_K, filter=None, where_document=None, **kwargs):
+        if where_document is not None:
+            _check_where_document(where_document)
+        return self.similarity_search_by_vector_with_score(self._embed_query(query), k, filter, where_document)
 
-    def similarity_search(self, query, k=DEFAULT_K, filter=None, **kwargs):
-        return [d for d, _ in self.similarity_search_with_score(query, k, filter)]
+    def similarity_search(self, query, k=DEFAULT_K, filter=None, where_document=None, **kwargs):
+        return [d for d, _ in self.similarity_search_with_score(query, k, filter, where_document)]
 
-    def similarity_search_with_cosine(self, query, k=DEFAULT_K, filter=None):
+    def similarity_search_with_cosine(self, query, k=DEFAULT_K, filter=None, where_document=None):
         """(Document, cosine similarity) pairs - the index's native score."""
-        return [(self._doc(r), c) for r, c in self._search_rows(self._embed_query(query), k, filter)]
+        if where_document is not None:
+            _check_where_document(where_document)
+        return [(self._doc(r), c)
+                for r, c in self._search_rows(self._embed_query(query), k, filter, where_document)]
 
-    def similarity_search_batch(self, queries, k=DEFAULT_K, filter=None):
+    def similarity_search_batch(self, queries, k=DEFAULT_K, filter=None, where_document=None):
         """Many queries in one encoder batch + one device search (the throughput path).
         With `filter`, the where-mask is built once on the device and ONE masked search
-        call serves the whole batch (mq_index_search_masked_batch)."""
+        call serves the whole batch (mq_index_search_masked_batch); `where_document` is ANDed
+        into that mask."""
+        if where_document is not None:
+            _check_where_document(where_document)
         n = 0 if self._index is None else len(self._index)
         if n == 0 or not queries or k <= 0:
             return [[] for _ in queries]
@@ -671,11 +863,10 @@ class HipChroma(VectorStoreBase):
             q = self._embedding_function.embed_array(list(queries))
         else:
             q = np.asarray(self._embedding_function.embed_documents(list(queries)), np.float32)
-        if filter:
-            kk = k if k <= _lib.MQ_MAX_K else _check_k(k, int(self._cols.mask(filter).sum()))
+        if filter or where_document is not None:
+            kk, bits = self._admit(k, filter, where_document)
             if kk == 0:
                 return [[] for _ in queries]
-            bits = self._cols.dmask(filter, self._device)
             _, rows = self._index.search_masked(q, int(kk), bits)
             return [[self._doc(int(r)) for r in row if r >= 0] for row in rows]
         kk = _check_k(k, n)
@@ -683,45 +874,51 @@ class HipChroma(VectorStoreBase):
         return [[self._doc(int(r)) for r in row if r >= 0] for row in ids]
 
     # ---- maximal marginal relevance --------------------------------------------------------
-    def _mmr_rows(self, q, k, fetch_k, lambda_mult, filter=None):
+    def _mmr_rows(self, q, k, fetch_k, lambda_mult, filter=None, where_document=None):
         """-> per query the rows LangChain's maximal_marginal_relevance picks from the top
         fetch_k, in selection order: one search + one selection launch on the device
         (mq_index_search_mmr).  fetch_k is clipped to the candidate rows (the store's, or the
-        filter's) and must then fit the device top-k; k > fetch_k returns fetch_k rows."""
+        filter's and where_document's) and must then fit the device top-k; k > fetch_k returns
+        fetch_k rows."""
+        if where_document is not None:
+            _check_where_document(where_document)
         q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self._dim or 1)
         n = 0 if self._index is None else len(self._index)
         if n == 0 or k <= 0 or fetch_k <= 0 or not len(q):
             return [[] for _ in range(len(q))]
         bits = None
-        if filter:
-            # the filter's row count decides between raising and clipping, as in _search_rows
-            if fetch_k > _lib.MQ_MAX_K:
-                fetch_k = _check_k(fetch_k, int(self._cols.mask(filter).sum()))
-                if fetch_k == 0:
-                    return [[] for _ in range(len(q))]
+        if filter or where_document is not None:
+            # the admitted-row count decides between raising and clipping, as in _search_rows
+            fetch_k, bits = self._admit(fetch_k, filter, where_document)
+            if fetch_k == 0:
+                return [[] for _ in range(len(q))]
             fetch_k = min(int(fetch_k), n)
-            bits = self._cols.dmask(filter, self._device)
         else:
             fetch_k = _check_k(fetch_k, n)
         _, ids = self._index.search_mmr(q, min(int(k), fetch_k), fetch_k, float(lambda_mult), bits)
         return [[int(r) for r in row if r >= 0] for row in ids]
 
     def max_marginal_relevance_search_by_vector(self, embedding, k=DEFAULT_K, fetch_k=20, lambda_mult=0.5,
-                                                filter=None, **kwargs):
+                                                filter=None, where_document=None, **kwargs):
         """LangChain's MMR search: the k of the fetch_k most similar rows that trade similarity
         to the query (weight lambda_mult) against similarity to the rows already picked
         (weight 1 - lambda_mult), as Documents in selection order."""
-        return [self._doc(r) for r in self._mmr_rows(embedding, k, fetch_k, lambda_mult, filter)[0]]
+        return [self._doc(r) for r in self._mmr_rows(embedding, k, fetch_k, lambda_mult, filter, where_document)[0]]
 
     def max_marginal_relevance_search(self, query, k=DEFAULT_K, fetch_k=20, lambda_mult=0.5, filter=None,
-                                      **kwargs):
+                                      where_document=None, **kwargs):
+        if where_document is not None:
+            _check_where_document(where_document)
         if (self._index is None or len(self._index) == 0) or k <= 0:
             return []
         return self.max_marginal_relevance_search_by_vector(self._embed_query(query), k, fetch_k, lambda_mult,
-                                                            filter)
+                                                            filter, where_document)
 
-    def max_marginal_relevance_search_batch(self, queries, k=DEFAULT_K, fetch_k=20, lambda_mult=0.5, filter=None):
+    def max_marginal_relevance_search_batch(self, queries, k=DEFAULT_K, fetch_k=20, lambda_mult=0.5, filter=None,
+                                            where_document=None):
         """Many queries: one encoder batch, one device search and one selection launch."""
+        if where_document is not None:
+            _check_where_document(where_document)
         n = 0 if self._index is None else len(self._index)
         if n == 0 or not queries or k <= 0:
             return [[] for _ in queries]
@@ -729,7 +926,8 @@ class HipChroma(VectorStoreBase):
             q = self._embedding_function.embed_array(list(queries))
         else:
             q = np.asarray(self._embedding_function.embed_documents(list(queries)), np.float32)
-        return [[self._doc(r) for r in rows] for rows in self._mmr_rows(q, k, fetch_k, lambda_mult, filter)]
+        return [[self._doc(r) for r in rows]
+                for rows in self._mmr_rows(q, k, fetch_k, lambda_mult, filter, where_document)]
 
     def _select_relevance_score_fn(self):
         if self.override_relevance_score_fn:
