@@ -377,6 +377,15 @@ int mq_encoder_set_graphs(mq_encoder* enc, int enabled);
  *                                rstd in their epilogue (no LayerNorm launch on the full-M
  *                                layers); 0 = a LayerNorm launch each.  Shapes outside the gate
  *                                run as with 0, bit for bit.
+ *   MQ_ENC_OPT_CLS_KFREE         CLS pooling, batched forward, L > 1, hidden <= 768: 1 (default) =
+ *                                the last layer projects neither K nor V - the CLS query is
+ *                                carried to the layer's input side (u = Wk_h^T q), one pass over
+ *                                the input rows gives the softmax-weighted row sums z, and ctx =
+ *                                Wv_h z + bv - and its closing LayerNorm, pooling and L2
+ *                                normalisation run in the FFN-down reduction; 0 = the K / V
+ *                                projection of every token and the attention kernel.  The same
+ *                                sums re-associated: results agree to fp32 rounding.  Mean pooling
+ *                                and L = 1 run as with 0, bit for bit.
  * Setting an option drops the handle's captured graphs. */
 #define MQ_ENC_OPT_ROWS_MAX 0
 #define MQ_ENC_OPT_ROWS_SPLITS 1
@@ -390,6 +399,7 @@ int mq_encoder_set_graphs(mq_encoder* enc, int enabled);
 #define MQ_ENC_OPT_X6_PRESPLIT 9
 #define MQ_ENC_OPT_ROWS_PLANES 10
 #define MQ_ENC_OPT_LN_FOLD 11
+#define MQ_ENC_OPT_CLS_KFREE 12
 int mq_encoder_set_option(mq_encoder* enc, int option, int value);
 int mq_encoder_get_option(const mq_encoder* enc, int option, int* value);
 int mq_encoder_set_timing(mq_encoder* enc, int enabled);
@@ -469,6 +479,18 @@ int mq_debug_ln_fold_weight(const float* W, const float* bias, const float* g, c
  * unchanged.  Asynchronous on `stream`. */
 int mq_debug_attention(const float* qkv, const int* mask, int B, int L, int H, int heads, float scale,
                        int variant, float* ctx, void* stream);
+/* The CLS query's attention without K and V (MQ_ENC_OPT_CLS_KFREE), steps u = Wk_h^T q, the pass
+ * over the input rows and ctx = Wv_h z + bv, on device buffers: ctx [B][H] = row 0 of
+ * softmax(scale q K^T over the keys with mask != 0) V per (sequence, head) with K = X Wk^T + bk
+ * (bk shifts a head's scores alike and drops out), V = X Wv^T + bv; a sequence whose keys are all
+ * masked gives 0.  q is [B][H] (the CLS rows' queries, bias included); x is [B*L][H]: the input
+ * rows X themselves (stats NULL), or raw rows y with stats [B*L][8] (mean, M2) partials per 96
+ * columns and X = LayerNorm(y; ln_g, ln_b, eps) (H = 768).  Wk, Wv are [H][H] row-major, bv [H],
+ * mask [B*L] int32; H == heads * 64, H <= 768.  Allocates its scratch (Wk^T, u, z): synchronous. */
+int mq_debug_cls_attention(const float* q, const float* x, const float* stats, const float* ln_g,
+                           const float* ln_b, float eps, const int* mask, int B, int L, int H, int heads,
+                           float scale, const float* Wk, const float* Wv, const float* bv, float* ctx,
+                           void* stream);
 /* The few-row forward's fused attention + output projection (K3o) on device buffers, launched
  * as forward_rows launches it: out = attention(qkv, mask) Wo^T + bo + resid, as heads / hg
  * planes [heads/hg][rows][H] (plane g holds head group g's share, plane 0 also bias +

@@ -584,7 +584,10 @@ __device__ __forceinline__ void ln_row_store(floatx4 (&x)[VPL], const float* __r
 // resid), slabs summed in order (the LN's reductions are block-wide, so the result
 // matches splitk_reduce_kernel<EPI_RESID> + ln_kernel to rounding).  A block reads its
 // whole row before writing it, so dst may alias resid row for row (stride H).
-template <int VPL>
+// POOL (the CLS-pooled last layer's FFN-down, MQ_ENC_OPT_CLS_KFREE): the rows are the
+// sequences' CLS rows and this LayerNorm the encoder's last, so the row is L2-normalised here,
+// v / max(||v||, 1e-12) as pool_kernel, and dst is the embedding - no pool launch.
+template <int VPL, bool POOL = false>
 __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(
     const float* __restrict__ slab, int S, int M, const float* __restrict__ bias,
     const float* resid, int ldr, const float* __restrict__ g, const float* __restrict__ b,
@@ -640,6 +643,19 @@ __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(
     var += x[i] * x[i];
   }
   const float rstd = 1.0f / sqrtf(block_sum(var) * (1.0f / H) + eps);
+  if constexpr (POOL) {
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      const int c = t + 256 * i;
+      x[i] = x[i] * rstd * g[c] + b[c];
+      ss += x[i] * x[i];
+    }
+    const float inv = 1.0f / fmaxf(sqrtf(block_sum(ss)), 1e-12f);
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) dst[(int64_t)row * H + t + 256 * i] = x[i] * inv;
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
     const int c = t + 256 * i;
@@ -1113,6 +1129,21 @@ __global__ __launch_bounds__(256) void ln_rows_inplace_kernel(float* x, int rows
 #pragma unroll
   for (int i = 0; i < VPL; ++i) v[i] = *reinterpret_cast<const floatx4*>(xr + (i * 64 + lane) * 4);
   ln_row_store<VPL>(v, g, b, eps, xr, lane);
+}
+// The same rows into a compact [rows][H] buffer, the source left as it is (the CLS_KFREE last
+// layer: its pass over the raw rows still reads row b L raw, with the partials).
+template <int VPL>
+__global__ __launch_bounds__(256) void ln_rows_kernel(const float* __restrict__ x, int rows, int64_t stride,
+                                                      const float* __restrict__ g, const float* __restrict__ b,
+                                                      float eps, float* __restrict__ dst) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const float* xr = x + (int64_t)row * stride;
+  floatx4 v[VPL];
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) v[i] = *reinterpret_cast<const floatx4*>(xr + (i * 64 + lane) * 4);
+  ln_row_store<VPL>(v, g, b, eps, dst + (int64_t)row * (VPL * 256), lane);
 }
 
 // ------------------------------------------------------------ K3 attention ----
@@ -1704,6 +1735,236 @@ __global__ __launch_bounds__(256) void ln_pool_kernel(const float* __restrict__ 
     *reinterpret_cast<floatx4*>(out + (int64_t)b * H + (i * 64 + lane) * 4) = x[i] * inv;
 }
 
+// ------------------------------------------- CLS attention without K and V ----
+// With CLS pooling the last layer attends from ONE query per sequence, so neither K nor V of
+// its tokens is needed (MQ_ENC_OPT_CLS_KFREE).  For head h of sequence b, with X the layer's
+// input rows, q the CLS query and Wk_h / Wv_h the head's 64 rows of Wk / Wv:
+//   score[t] = x_t . u / sqrt(dh) + q . bk_h      u = Wk_h^T q           (gemm_heads_kernel)
+//   z        = sum_t softmax(score)[t] x_t                               (cls_pass_kernel)
+//   ctx      = Wv_h z + bv_h                                             (gemm_heads_kernel)
+// q . bk_h is the same for every key and drops out of the softmax; sum_t p[t] = 1 carries bv
+// through.  The all-token [M, 2H] projection and the attention launch become two B-row GEMMs
+// and one pass over X: the same sums re-associated, fp32 throughout.
+
+// W [R][C] -> out [C][R] (Wk^T of the last layer, once per weight load).
+__global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ W, int R, int C,
+                                                        float* __restrict__ out) {
+  __shared__ float tile[32][33];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
+  for (int j = ty; j < 32; j += 8)
+    if (r0 + j < R && c0 + tx < C) tile[j][tx] = W[(int64_t)(r0 + j) * C + c0 + tx];
+  __syncthreads();
+  for (int j = ty; j < 32; j += 8)
+    if (c0 + j < C && r0 + tx < R) out[(int64_t)(c0 + j) * R + r0 + tx] = tile[tx][j];
+}
+
+// One exact-f32 GEMM per head in one launch: for head h, out_h[M][N] = A_h[M][K] . W_h[N][K]^T
+// (+ live[row] bias[h N + col]), with A_h = A + h a_head (row stride lda), W_h = W + h w_head
+// (row stride ldw), out_h = out + h o_head (row stride ldo).  Workgroup (h, tile, s) runs its
+// tile over K-chunk s of S and writes plane s (o_plane floats apart; S = 1: the bias goes in
+// here) - every stored element is one k-ordered MFMA chain, whatever M is.  An exact-f32 MFMA
+// chain is serial in k (64 cycles a step), so the deep product is cut into kClsCtxSplits
+// chunks, a constant: the planes are summed in order by cls_ctx_reduce_kernel.
+//   u   = Wk_h^T q:  A = q [B][H] (a_head 64), W = Wk^T [H][H] (w_head 64), K = 64, N = H
+//   ctx = Wv_h z:    A = z [B][heads][H] (a_head H), W = Wv (w_head 64 H), K = H, N = 64, S = 4
+constexpr int kClsCtxSplits = 4;
+template <class T>
+__global__ __launch_bounds__(256, 2) void gemm_heads_kernel(const float* __restrict__ A, int lda, int a_head,
+                                                            const float* __restrict__ W, int ldw, int w_head,
+                                                            const float* __restrict__ bias,
+                                                            const float* __restrict__ live, int M, int N, int K,
+                                                            float* __restrict__ out, int ldo, int o_head, int S,
+                                                            int64_t o_plane) {
+  __shared__ __attribute__((aligned(16))) float lds[2 * T::STAGE_FLOATS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wm = wave / T::WAVES_N, wn = wave % T::WAVES_N;
+  const int tiles_n = (N + T::BN - 1) / T::BN;
+  const int per_head = ((M + T::BM - 1) / T::BM) * tiles_n;
+  const int sidx = blockIdx.x % S, ht = blockIdx.x / S;
+  const int head = ht / per_head, tile = ht % per_head;
+  const int Kc = K / S;
+  const int m0 = (tile / tiles_n) * T::BM;
+  const int n0 = (tile % tiles_n) * T::BN;
+  auto coords = [&](int, int& mm0, int64_t& nn0) {
+    mm0 = m0;
+    nn0 = n0;
+  };
+  float* dst = out + sidx * o_plane + (int64_t)head * o_head;
+  auto epi = [&](int, floatx16(&acc)[T::TM][T::TN], float*) {
+#pragma unroll
+    for (int tn = 0; tn < T::TN; ++tn) {
+      const int col = n0 + wn * T::WN + tn * 32 + (lane & 31);
+      if (col >= N) continue;
+      const float bv = bias ? bias[head * N + col] : 0.f;
+#pragma unroll
+      for (int tm = 0; tm < T::TM; ++tm)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int row = m0 + wm * T::WM + acc_row(tm, e, lane);
+          if (row < M) dst[(int64_t)row * ldo + col] = bias ? __fmaf_rn(live[row], bv, acc[tm][tn][e]) : acc[tm][tn][e];
+        }
+    }
+  };
+  walk_tiles<T>(lds, 1,
+                TileOperands{A + (int64_t)head * a_head + sidx * Kc, lda, M, W + (int64_t)head * w_head + sidx * Kc, ldw,
+                             N, Kc},
+                coords, epi);
+}
+
+// ctx [B][H] = the kClsCtxSplits planes of Wv_h z summed in order + live[row] bv (float4 each).
+__global__ __launch_bounds__(256) void cls_ctx_reduce_kernel(const float* __restrict__ part, int B, int H,
+                                                             const float* __restrict__ bv,
+                                                             const float* __restrict__ live,
+                                                             float* __restrict__ ctx) {
+  const int64_t i4 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int n4 = H / 4;
+  if (i4 >= (int64_t)B * n4) return;
+  const int row = (int)(i4 / n4), c = (int)(i4 % n4) * 4;
+  floatx4 v = sum_slabs(part + (int64_t)row * H + c, (int64_t)B * H, kClsCtxSplits);
+  const float lv = live[row];
+  const floatx4 b = *reinterpret_cast<const floatx4*>(bv + c);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = __fmaf_rn(lv, b[j], v[j]);
+  *reinterpret_cast<floatx4*>(ctx + (int64_t)row * H + c) = v;
+}
+
+// The pass over the last layer's input rows: one workgroup per sequence with one wave per head
+// (H threads).  Rows arrive once, kClsChunk at a time, into LDS (the next chunk's loads in
+// flight under this one's arithmetic).  Wave h keeps head h's u in registers, takes its dot
+// products with the chunk's rows and advances the head's online softmax on lanes 0..15, one
+// key each (running max / sum, the chunk's probabilities, the rescale alpha of what is
+// accumulated); then thread c adds the chunk into column c of every head's z.  Any L: the
+// state is O(1) in it.
+// FOLD: x holds raw rows y with (mean, M2) partials (the LayerNorm-fold layers leave LN2
+// unapplied): a row is staged as n_t = (y_t - mu_t) rho_t (ln_merge, as every other consumer) and
+// gamma / beta are applied algebraically - score = n_t . (g o u) (+ beta . u, the same for every
+// key: dropped with q . bk), z = g o sum_t p_t n_t + beta.
+// A key with mask 0 gets probability exactly 0; a sequence with no live key gets z = 0, live = 0
+// (ctx = 0 then, as attention_kernel gives).  Nothing here depends on B or on blockIdx beyond
+// the sequence's own rows.
+constexpr int kClsChunk = 16;
+template <int VPL, bool FOLD>
+__global__ __launch_bounds__(256 * VPL) void cls_pass_kernel(const float* __restrict__ x,
+                                                             const float* __restrict__ stats,
+                                                             const float* __restrict__ g,
+                                                             const float* __restrict__ be, float eps,
+                                                             const float* __restrict__ u,
+                                                             const int* __restrict__ mask, int L, float scale,
+                                                             float* __restrict__ z, float* __restrict__ live) {
+  constexpr int H = VPL * 256, HEADS = H / kDh, CH = kClsChunk;
+  constexpr int TPR = H / CH;  // threads per staged row: 4 float4 each
+  static_assert(CH == 16 && (CH * H + CH * HEADS + 2 * HEADS) * 4 <= 64 * 1024, "LDS: one chunk of rows, scores");
+  __shared__ __attribute__((aligned(16))) float xs[CH * H];
+  __shared__ __attribute__((aligned(16))) float ps[CH * HEADS];  // [key][head] probabilities
+  __shared__ __attribute__((aligned(16))) float alpha_s[HEADS];
+  __shared__ float l_s[HEADS];
+  const int t = threadIdx.x, lane = t & 63, h = t >> 6;
+  const int b = blockIdx.x;
+  const int64_t row0 = (int64_t)b * L;
+  const int lrow = t / TPR, lc4 = t % TPR;  // this thread's row of a chunk and first float4 in it
+  floatx4 ur[VPL];
+#pragma unroll
+  for (int i = 0; i < VPL; ++i) {
+    ur[i] = *reinterpret_cast<const floatx4*>(u + ((int64_t)b * HEADS + h) * H + (i * 64 + lane) * 4);
+    if constexpr (FOLD) ur[i] *= *reinterpret_cast<const floatx4*>(g + (i * 64 + lane) * 4);
+  }
+  floatx4 xr[4], sr[kLnMaxParts / 2];
+  int mk = 0;
+  auto fetch = [&](int k0) {
+    const int64_t row = row0 + min(k0 + lrow, L - 1);  // rows past L repeat the last (probability 0)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) xr[j] = *reinterpret_cast<const floatx4*>(x + row * H + (lc4 + TPR * j) * 4);
+    if constexpr (FOLD) {
+      const floatx4* sp = reinterpret_cast<const floatx4*>(stats + row * (2 * kLnMaxParts));
+#pragma unroll
+      for (int i = 0; i < kLnMaxParts / 2; ++i) sr[i] = sp[i];
+    }
+    mk = lane < CH && k0 + lane < L ? mask[row0 + k0 + lane] : 0;
+  };
+  float zacc[HEADS];
+#pragma unroll
+  for (int hh = 0; hh < HEADS; ++hh) zacc[hh] = 0.f;
+  float m_run = -INFINITY, l_run = 0.f;  // head h's softmax state, the same on every lane of wave h
+  fetch(0);
+  for (int k0 = 0; k0 < L; k0 += CH) {
+    if constexpr (FOLD) {
+      float mu, rho;
+      ln_merge(sr, eps, mu, rho);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) xr[j] = (xr[j] - mu) * rho;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) *reinterpret_cast<floatx4*>(xs + lrow * H + (lc4 + TPR * j) * 4) = xr[j];
+    const int live_key = mk;
+    __syncthreads();
+    if (k0 + CH < L) fetch(k0 + CH);
+    // head h: the chunk's dot products, every lane ending with all of them
+    float d[CH];
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+      float a = 0.f;
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) {
+        const floatx4 v = *reinterpret_cast<const floatx4*>(xs + k * H + (i * 64 + lane) * 4);
+        a = fmaf(v.x, ur[i].x, fmaf(v.y, ur[i].y, fmaf(v.z, ur[i].z, fmaf(v.w, ur[i].w, a))));
+      }
+      d[k] = a;
+    }
+#pragma unroll
+    for (int k = 0; k < CH; ++k) d[k] = wave_sum_fast(d[k]);
+    // lanes 0..15: key k0 + lane (the other lanes carry -inf / 0 through the 16-lane reductions)
+    float sc = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < CH; ++k) sc = lane == k ? d[k] : sc;
+    sc = live_key != 0 ? sc * scale : -INFINITY;
+    float tmax = sc;
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) tmax = fmaxf(tmax, __shfl_xor(tmax, off));
+    tmax = __shfl(tmax, 0);
+    const float m_new = fmaxf(m_run, tmax);
+    const float alpha = m_new == -INFINITY ? 1.f : expf(m_run - m_new);
+    const float p = sc == -INFINITY ? 0.f : expf(sc - m_new);
+    float psum = p;
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) psum += __shfl_xor(psum, off);
+    psum = __shfl(psum, 0);
+    l_run = l_run * alpha + psum;
+    m_run = m_new;
+    if (lane < CH) ps[lane * HEADS + h] = p;
+    if (lane == 0) alpha_s[h] = alpha;
+    __syncthreads();
+    // column t of every head's z
+#pragma unroll
+    for (int q4 = 0; q4 < HEADS / 4; ++q4) {
+      const floatx4 a = *reinterpret_cast<const floatx4*>(alpha_s + 4 * q4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) zacc[4 * q4 + e] *= a[e];
+    }
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+      const float xv = xs[k * H + t];
+#pragma unroll
+      for (int q4 = 0; q4 < HEADS / 4; ++q4) {
+        const floatx4 pp = *reinterpret_cast<const floatx4*>(ps + k * HEADS + 4 * q4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) zacc[4 * q4 + e] = fmaf(pp[e], xv, zacc[4 * q4 + e]);
+      }
+    }
+    __syncthreads();  // the next chunk overwrites xs / ps
+  }
+  if (lane == 0) l_s[h] = l_run;
+  __syncthreads();
+#pragma unroll
+  for (int hh = 0; hh < HEADS; ++hh) {
+    const float l = l_s[hh];
+    float v = l > 0.f ? zacc[hh] * (1.0f / l) : 0.f;
+    if constexpr (FOLD) v = l > 0.f ? fmaf(v, g[t], be[t]) : 0.f;
+    z[((int64_t)b * HEADS + hh) * H + t] = v;
+  }
+  if (t == 0) live[b] = l_s[0] > 0.f ? 1.f : 0.f;
+}
+
 }  // namespace mq
 
 // ================================================================ host side =====
@@ -1967,6 +2228,11 @@ void launch_gemm_ln_in(const GemmArgs& g, const LnArgs& ln, int num_cus, hipStre
 #define MQ_LN_FOLD_DEFAULT 1
 #endif
 constexpr bool kLnFoldDefault = MQ_LN_FOLD_DEFAULT != 0;
+// MQ_ENC_OPT_CLS_KFREE's default (DESIGN.md section 4 has the A/B that decides it)
+#ifndef MQ_CLS_KFREE_DEFAULT
+#define MQ_CLS_KFREE_DEFAULT 1
+#endif
+constexpr bool kClsKfreeDefault = MQ_CLS_KFREE_DEFAULT != 0;
 
 // Stage labels for the optional per-kernel-class event timeline.
 enum Stage { ST_EMBED = 0, ST_QKV, ST_ATTN, ST_OPROJ, ST_LN, ST_FFN_UP, ST_FFN_DOWN, ST_POOL, ST_N };
@@ -2019,6 +2285,9 @@ struct mq_encoder {
   bool ln_fold = kLnFoldDefault;  // split-f32 batched forward: LayerNorm folded into the GEMMs (LnFold)
   Buf wfold3, wfoldf, sfold;    // its gamma-scaled weights (W3 images / fp32) and s, c vectors
   bool rows_planes = false;     // few-row forward: keep the two-plane hand-offs (no FL_ACC merge)
+  bool cls_kfree = kClsKfreeDefault;  // CLS pooling, batched forward: the last layer without K / V
+  Buf wkt;                      // its Wk^T of the last layer [H][H], built at weight load
+  Buf cls;                      // its [B] rows: normalised CLS rows, q (H each), u, z (heads H each), live
   bool use_graphs = false;  // eager measured faster for one query (0.628 vs 0.645 ms: the
                             // graph path stages ids / mask / out through its own buffers)
   uint64_t graph_clock = 0;
@@ -2144,6 +2413,21 @@ int build_frag16(mq_encoder* e) {
   return MQ_OK;
 }
 
+// Wk^T of the last layer (MQ_ENC_OPT_CLS_KFREE: u = Wk_h^T q reads it K-contiguous), 4 H^2
+// bytes, built with the other weight images at load when the pooling is CLS.  Synchronous.
+int build_wkt(mq_encoder* e) {
+  const int H = e->cfg.hidden;
+  if (e->cfg.pooling != MQ_POOL_CLS || e->layers.empty()) return MQ_OK;
+  DeviceGuard dg(e->device);
+  int rc = e->wkt.ensure((size_t)H * H);
+  if (rc) return rc;
+  hipLaunchKernelGGL(transpose_kernel, dim3(H / 32, H / 32), dim3(256), 0, nullptr,
+                     e->layers.back().wqkv + (int64_t)H * H, H, H, e->wkt.p);
+  MQ_HIP(hipGetLastError());
+  MQ_HIP(hipStreamSynchronize(nullptr));
+  return MQ_OK;
+}
+
 template <int EPI>
 void gemm(mq_encoder* e, const GemmArgs& g, int stage, hipStream_t s) {
   e->tl.mark(s, stage);
@@ -2196,10 +2480,84 @@ void gemm_resid_ln(mq_encoder* e, const GemmArgs& g, const float* lng, const flo
                        lnb, e->cfg.ln_eps, x);
 }
 
+// The CLS_KFREE last layer's buffers inside mq_encoder::cls for B sequences.
+struct ClsBufs {
+  float *xc, *q, *u, *z, *part, *live;  // part: the ctx product's kClsCtxSplits planes [B][H]
+  static size_t floats(int B, int H, int heads) {
+    return (size_t)B * ((2 + kClsCtxSplits) * H + 2 * (size_t)heads * H + 1);
+  }
+  ClsBufs(float* p, int B, int H, int heads)
+      : xc(p), q(xc + (size_t)B * H), u(q + (size_t)B * H), z(u + (size_t)B * heads * H),
+        part(z + (size_t)B * heads * H), live(part + (size_t)kClsCtxSplits * B * H) {}
+};
+
+// u [B][heads][H] = Wk_h^T q for every head: 32 x 128 tiles, 64 deep.
+void launch_cls_u(int B, int H, int heads, const float* q, const float* wkt, float* u, hipStream_t s) {
+  using T = F32Tile<1, 4, 1, 1>;
+  const int tiles = ((B + T::BM - 1) / T::BM) * ((H + T::BN - 1) / T::BN);
+  hipLaunchKernelGGL((gemm_heads_kernel<T>), dim3(tiles * heads), dim3(256), 0, s, q, H, kDh, wkt, H, kDh, nullptr,
+                     nullptr, B, H, kDh, u, heads * H, H, 1, (int64_t)0);
+}
+
+// z (the pass over the input rows: x normalised, or raw with stats / g / be) and ctx [B][H] =
+// Wv_h z + live bv (64 x 64 tiles over H / kClsCtxSplits each into `part`, then the ordered
+// sum).  H = 256 / 512 / 768.
+void launch_cls_ctx(int B, int L, int H, int heads, float scale, const float* x, const float* stats,
+                    const float* g, const float* be, float eps, const float* u, const int* mask, const float* wv,
+                    const float* bv, float* z, float* part, float* live, float* ctx, hipStream_t s) {
+  auto pass = [&](auto vpl) {
+    constexpr int VPL = decltype(vpl)::value;
+    if (stats)
+      hipLaunchKernelGGL((cls_pass_kernel<VPL, true>), dim3(B), dim3(256 * VPL), 0, s, x, stats, g, be, eps, u, mask, L,
+                         scale, z, live);
+    else
+      hipLaunchKernelGGL((cls_pass_kernel<VPL, false>), dim3(B), dim3(256 * VPL), 0, s, x, stats, g, be, eps, u, mask, L,
+                         scale, z, live);
+  };
+  if (H == 256)
+    pass(IC<1>{});
+  else if (H == 512)
+    pass(IC<2>{});
+  else
+    pass(IC<3>{});
+  using T = F32Tile<2, 2, 1, 1>;
+  const int tiles = (B + T::BM - 1) / T::BM;
+  hipLaunchKernelGGL((gemm_heads_kernel<T>), dim3(tiles * heads * kClsCtxSplits), dim3(256), 0, s, z, heads * H, H, wv, H,
+                     kDh * H, nullptr, nullptr, B, kDh, H, part, H, kDh, kClsCtxSplits, (int64_t)B * H);
+  hipLaunchKernelGGL(cls_ctx_reduce_kernel, dim3((unsigned)(((int64_t)B * H / 4 + 255) / 256)), dim3(256), 0, s, part, B,
+                     H, bv, live, ctx);
+}
+
+// The CLS-pooled last layer's FFN-down with the encoder's closing LayerNorm, pooling and L2
+// normalisation (CLS_KFREE): out [M][H] = l2norm(LN(A W^T + b + resid)).  Split-K: the ordered
+// slab reduction does all of it; else the GEMM through y (g.out) and ln_pool_kernel.
+template <int VPL>
+void gemm_resid_ln_pool(mq_encoder* e, const GemmArgs& g, const float* lng, const float* lnb, const int* mask,
+                        float* out, int stage, hipStream_t s) {
+  const int H = VPL * 256;
+  const int S = splitk_factor(g, e->num_cus, e->splitk_max, e->splitk_tiles);
+  if (S && g.ldr == H && g.N == H) {
+    e->tl.mark(s, stage);
+    launch_splitk_gemm(g, S, s);
+    e->tl.mark(s, ST_POOL);
+    hipLaunchKernelGGL((splitk_reduce_ln_kernel<VPL, true>), dim3((unsigned)g.M), dim3(256), 0, s, g.slab, S, g.M,
+                       g.bias, g.resid, g.ldr, lng, lnb, e->cfg.ln_eps, out);
+    return;
+  }
+  gemm<EPI_RESID>(e, g, stage, s);
+  e->tl.mark(s, ST_POOL);
+  hipLaunchKernelGGL((ln_pool_kernel<VPL>), dim3((unsigned)((g.M + 3) / 4)), dim3(256), 0, s, g.out, 1, (int64_t)0, mask,
+                     g.M, 1, 1, MQ_POOL_CLS, lng, lnb, e->cfg.ln_eps, out);
+}
+
 // One forward.  With CLS pooling the last layer only needs the CLS rows after its
-// attention: its QKV projection runs on all tokens (keys / values), attention on the
-// first 32-query tile, and the output projection, LayerNorms and FFN on the B CLS
-// rows (strided views of the activations) - identical CLS outputs, ~8% less work.
+// attention: the output projection, LayerNorms and FFN run on the B CLS rows - identical CLS
+// outputs, ~8% less work.  Its attention has one query per sequence, so (MQ_ENC_OPT_CLS_KFREE,
+// the section above cls_pass_kernel) it projects neither K nor V: Q for the B CLS rows, u =
+// Wk_h^T q, one pass over the layer's input rows, ctx = Wv_h z + bv, then the tail, whose
+// FFN-down reduction also applies the closing LayerNorm, the pooling and the L2 norm.  With the
+// option off: K and V for every token ([M, 2H]), attention on the first 32-query tile, the tail
+// on strided views of the activations, and a pool launch.
 template <int VPL>
 int forward_vpl(mq_encoder* e, const int* ids, const int* mask, int B, int L, float* out,
                 hipStream_t s) {
@@ -2231,6 +2589,7 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* mask, int B, int L, fl
   float* fst1 = e->lnst.p;
   float* fst2 = e->lnst.p + (size_t)2 * M * nt;
   bool raw = false;  // fold: x holds the previous layer's raw FFN-down sum (+ fst2), not LN2 of it
+  bool pooled = false;  // CLS_KFREE: the last FFN-down's reduction has written the embeddings
   auto fold_gemm = [&](auto epi, GemmArgs g, int stage) {
     e->tl.mark(s, stage);
     if (!e->x6_presplit) g.W3 = nullptr;
@@ -2259,7 +2618,12 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* mask, int B, int L, fl
     const bool cls_only = c.pooling == MQ_POOL_CLS && li + 1 == e->layers.size();
     // rows this layer carries past attention: all M tokens, or the B CLS rows
     const int rows = cls_only ? B : M;
-    const int stride = cls_only ? L * H : H;  // row stride of x / ctx views
+    int stride = cls_only ? L * H : H;  // row stride of the x / ctx views
+    const float* resid = e->x.p;        // out-proj's residual rows (stride ldr)
+    int ldr = stride;
+    // the last layer without K / V (cls_pass_kernel holds hidden <= 768 in LDS)
+    const bool kfree = cls_only && L > 1 && e->cls_kfree && VPL <= 3 && e->wkt.p != nullptr &&
+                       e->cls.n >= ClsBufs::floats(B, H, c.heads);
     // QKV input: x, or (deferred LN2 of the previous layer) y normalised while staged,
     // the column-0 tiles writing LN2(y) to x for the residual and the CLS-row Q GEMM
     const float* qkv_in = y_pending ? e->y.p : e->x.p;
@@ -2288,7 +2652,30 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* mask, int B, int L, fl
         gemm<EPI_BIAS>(e, g, ST_QKV, s);
       }
     };
-    if (cls_only && L > 1) {
+    if (kfree) {
+      const ClsBufs cb(e->cls.p, B, H, c.heads);
+      // the layer's input as the pass reads it: normalised rows in x, or raw rows with their
+      // partials and the previous layer's LN2 (the fold's x + fst2, LN-on-load's y + st2)
+      const float* xin = raw ? e->x.p : y_pending ? e->y.p : e->x.p;
+      const float* xst = raw ? fst2 : y_pending ? st2 : nullptr;
+      if (xst) {
+        // The normalised CLS rows go to a SEPARATE [B, H] buffer (the Q GEMM and the tail's
+        // residual read that): row b L of the raw buffer stays raw for the pass below.
+        e->tl.mark(s, ST_LN);
+        hipLaunchKernelGGL((ln_rows_kernel<VPL>), dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, xin, B, (int64_t)L * H,
+                           prev->ln2g, prev->ln2b, c.ln_eps, cb.xc);
+        resid = cb.xc;
+        ldr = H;
+      }
+      GemmArgs q{e->slab.p, e->slab.n, resid, ldr, w.wqkv, w.bqkv, nullptr, 0, cb.q, H, B, H, H, lnt};
+      q.W3 = w.wqkv3;
+      gemm<EPI_BIAS>(e, q, ST_QKV, s);
+      launch_cls_u(B, H, c.heads, cb.q, e->wkt.p, cb.u, s);
+      e->tl.mark(s, ST_ATTN);
+      launch_cls_ctx(B, L, H, c.heads, scale, xin, xst, xst ? prev->ln2g : nullptr, xst ? prev->ln2b : nullptr,
+                     c.ln_eps, cb.u, mask, w.wqkv + (int64_t)2 * H * H, w.bqkv + 2 * H, cb.z, cb.part, cb.live, e->ctx.p, s);
+      stride = H;  // ctx is compact
+    } else if (cls_only && L > 1) {
       // only the CLS rows need queries: K and V for every token ([M, 2H] into qkv columns
       // H..3H), Q for the B CLS rows (every L-th row of x into row b*L of qkv)
       GemmArgs kv{e->slab.p, e->slab.n, qkv_in, H, w.wqkv + (int64_t)H * H, w.bqkv + H, nullptr, 0, e->qkv.p + H,
@@ -2311,12 +2698,14 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* mask, int B, int L, fl
     y_pending = false;
     const bool resid_raw = raw && fold_layer;  // (the tail's residual rows were normalised above)
     raw = false;
-    e->tl.mark(s, ST_ATTN);
-    const int qt = cls_only ? 1 : q_tiles;
-    launch_attention(B, L, c.heads, qt, H, scale, e->qkv.p, mask, e->ctx.p, s);
+    if (!kfree) {
+      e->tl.mark(s, ST_ATTN);
+      const int qt = cls_only ? 1 : q_tiles;
+      launch_attention(B, L, c.heads, qt, H, scale, e->qkv.p, mask, e->ctx.p, s);
+    }
     const bool lnl_layer = lnl && !cls_only;
     // x = LN1(x + ctx Wo^T + bo)  (compact [rows, H], through y) - or, deferred, y + partials
-    GemmArgs oproj{e->slab.p, e->slab.n, e->ctx.p, stride, w.wo, w.bo, e->x.p, stride, e->y.p, H, rows, H, H, lnt};
+    GemmArgs oproj{e->slab.p, e->slab.n, e->ctx.p, stride, w.wo, w.bo, resid, ldr, e->y.p, H, rows, H, H, lnt};
     oproj.W3 = w.wo3;
     if (fold_layer) {  // y = ctx Wo^T + bo + (LN2_prev(x) or x), raw, + its partials
       oproj.lf.stats_out = fst1;
@@ -2379,15 +2768,20 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* mask, int B, int L, fl
       e->tl.mark(s, ST_FFN_DOWN);
       launch_gemm_stats(down, stats_out(st2), e->num_cus, s);
       y_pending = true;
+    } else if (kfree) {  // the encoder's end: LN2, CLS pooling and the L2 norm with the reduction
+      gemm_resid_ln_pool<VPL>(e, down, w.ln2g, w.ln2b, mask, out, ST_FFN_DOWN, s);
+      pooled = true;
     } else {
       gemm_resid_ln<VPL>(e, down, w.ln2g, w.ln2b, e->x.p, ST_FFN_DOWN, s);
     }
     prev = &w;
   }
-  e->tl.mark(s, ST_POOL);
-  const bool pruned = c.pooling == MQ_POOL_CLS;  // x holds [B, H] CLS rows
-  hipLaunchKernelGGL((pool_kernel<VPL>), dim3((B + 3) / 4), dim3(256), 0, s, e->x.p, mask, B,
-                     pruned ? 1 : L, c.pooling, out);
+  if (!pooled) {
+    e->tl.mark(s, ST_POOL);
+    const bool pruned = c.pooling == MQ_POOL_CLS;  // x holds [B, H] CLS rows
+    hipLaunchKernelGGL((pool_kernel<VPL>), dim3((B + 3) / 4), dim3(256), 0, s, e->x.p, mask, B,
+                       pruned ? 1 : L, c.pooling, out);
+  }
   e->tl.close(s);
   MQ_HIP(hipGetLastError());
   return MQ_OK;
@@ -2686,7 +3080,8 @@ constexpr size_t kMaxGraphs = 6;
 int launch_graph(mq_encoder* e, int B, int L, hipStream_t s) {
   const std::vector<const void*> bufs = {e->weights.p, e->x.p,   e->y.p,      e->qkv.p,
                                          e->ctx.p,     e->ffn.p, e->slab.p,   e->io_out.p,
-                                         e->io_ids,    e->io_mask,  e->w3.p,   e->wfrag.p};
+                                         e->io_ids,    e->io_mask,  e->w3.p,   e->wfrag.p,
+                                         e->wkt.p,     e->cls.p};
   mq_encoder::Graph* hit = nullptr;
   for (auto& g : e->graphs)
     if (g.B == B && g.L == L && g.precision == e->precision && g.bufs == bufs) hit = &g;
@@ -2790,7 +3185,7 @@ int mq_encoder_destroy(mq_encoder* e) {
   {
     DeviceGuard dg(e->device);
     for (Buf* b : {&e->weights, &e->x, &e->y, &e->qkv, &e->ctx, &e->ffn, &e->io_out, &e->slab, &e->w3, &e->wfrag,
-                   &e->lnst})
+                   &e->lnst, &e->wkt, &e->cls})
       b->release();
     if (e->io_ids) (void)hipFree(e->io_ids);
     if (e->io_mask) (void)hipFree(e->io_mask);
@@ -2848,6 +3243,8 @@ int mq_encoder_load_weights(mq_encoder* e, const float* blob, int64_t n_floats) 
     rc = build_frag16(e);
     if (rc) return rc;
   }
+  rc = build_wkt(e);
+  if (rc) return rc;
   return build_w3(e);  // (re)split the new weights when the split-f32 precision is selected
 }
 
@@ -2976,6 +3373,33 @@ int mq_debug_attn_oproj(const float* qkv, const int* mask, int B, int L, int H, 
   return MQ_OK;
 }
 
+int mq_debug_cls_attention(const float* q, const float* x, const float* stats, const float* ln_g,
+                           const float* ln_b, float eps, const int* mask, int B, int L, int H, int heads,
+                           float scale, const float* Wk, const float* Wv, const float* bv, float* ctx,
+                           void* stream) {
+  clear_error();
+  MQ_CHECK_ARG(q && x && mask && Wk && Wv && bv && ctx, "NULL buffer");
+  MQ_CHECK_ARG(B > 0 && L > 0 && heads > 0 && H == heads * kDh, "bad shape B=%d L=%d H=%d heads=%d", B, L, H, heads);
+  MQ_CHECK_ARG(H == 256 || H == 512 || H == 768, "hidden must be 256 / 512 / 768 (got %d)", H);
+  MQ_CHECK_ARG(!stats || (ln_g && ln_b && H == kLnPartW * kLnMaxParts), "stats need ln_g, ln_b and H = %d",
+               kLnPartW * kLnMaxParts);
+  hipStream_t s = (hipStream_t)stream;
+  float* scratch = nullptr;  // Wk^T, then the forward's CLS buffers
+  const size_t wkt_floats = (size_t)H * H;
+  if (hipMalloc((void**)&scratch, (wkt_floats + ClsBufs::floats(B, H, heads)) * 4) != hipSuccess)
+    MQ_FAIL(MQ_ENOMEM, "scratch allocation failed");
+  const ClsBufs cb(scratch + wkt_floats, B, H, heads);
+  hipLaunchKernelGGL(transpose_kernel, dim3(H / 32, H / 32), dim3(256), 0, s, Wk, H, H, scratch);
+  launch_cls_u(B, H, heads, q, scratch, cb.u, s);
+  launch_cls_ctx(B, L, H, heads, scale, x, stats, ln_g, ln_b, eps, cb.u, mask, Wv, bv, cb.z, cb.part, cb.live, ctx, s);
+  hipError_t err = hipGetLastError();
+  const hipError_t serr = hipStreamSynchronize(s);
+  (void)hipFree(scratch);
+  if (err == hipSuccess) err = serr;
+  if (err != hipSuccess) MQ_FAIL(MQ_EHIP, "CLS attention failed: %s", hipGetErrorString(err));
+  return MQ_OK;
+}
+
 int mq_encoder_set_graphs(mq_encoder* e, int enabled) {
   clear_error();
   MQ_CHECK_ARG(e, "NULL encoder");
@@ -3037,6 +3461,10 @@ int mq_encoder_set_option(mq_encoder* e, int option, int value) {
       MQ_CHECK_ARG(value == 0 || value == 1, "ln_fold must be 0 or 1 (got %d)", value);
       e->ln_fold = value != 0;
       break;
+    case MQ_ENC_OPT_CLS_KFREE:
+      MQ_CHECK_ARG(value == 0 || value == 1, "cls_kfree must be 0 or 1 (got %d)", value);
+      e->cls_kfree = value != 0;
+      break;
     default:
       MQ_FAIL(MQ_EINVAL, "unknown encoder option %d", option);
   }
@@ -3062,6 +3490,7 @@ int mq_encoder_get_option(const mq_encoder* e, int option, int* value) {
     case MQ_ENC_OPT_X6_PRESPLIT: *value = e->x6_presplit ? 1 : 0; break;
     case MQ_ENC_OPT_ROWS_PLANES: *value = e->rows_planes ? 1 : 0; break;
     case MQ_ENC_OPT_LN_FOLD: *value = e->ln_fold ? 1 : 0; break;
+    case MQ_ENC_OPT_CLS_KFREE: *value = e->cls_kfree ? 1 : 0; break;
     default: MQ_FAIL(MQ_EINVAL, "unknown encoder option %d", option);
   }
   return MQ_OK;
@@ -3110,10 +3539,13 @@ int mq_encoder_embed(mq_encoder* e, const int32_t* ids, const int32_t* mask, int
   rc = build_fold(e);  // (MQ_ENC_OPT_LN_FOLD: the folded weights of the current mode, once)
   if (rc) return rc;
   const size_t ln_parts = (e->ln_on_load || e->ln_fold) && M > 256 ? (size_t)4 * M * std::max(1, c.hidden / kLnPartW) : 0;
+  // (MQ_ENC_OPT_CLS_KFREE: the last layer's CLS-row buffers)
+  const size_t cls_floats = e->cls_kfree && c.pooling == MQ_POOL_CLS && L > 1 ? ClsBufs::floats(B, c.hidden, c.heads) : 0;
   for (auto bn : {std::make_pair(&e->x, M * c.hidden), std::make_pair(&e->y, (M <= (size_t)kRowsMax ? 4 : 1) * M * c.hidden),
                   std::make_pair(&e->ctx, M * c.hidden), std::make_pair(&e->qkv, M * 3 * c.hidden),
                   // (the few-row FFN output is frag16: whole 16-row blocks)
-                  std::make_pair(&e->ffn, (M + 15) / 16 * 16 * c.ffn), std::make_pair(&e->lnst, ln_parts)}) {
+                  std::make_pair(&e->ffn, (M + 15) / 16 * 16 * c.ffn), std::make_pair(&e->lnst, ln_parts),
+                  std::make_pair(&e->cls, cls_floats)}) {
     rc = bn.first->ensure(bn.second);
     if (rc) return rc;
   }

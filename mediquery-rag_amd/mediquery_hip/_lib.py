@@ -31,6 +31,7 @@ MQ_ENC_OPT_SPLITK_TILES, MQ_ENC_OPT_LN_ON_LOAD, MQ_ENC_OPT_RESIDENT_LAYERS = 6, 
 MQ_ENC_OPT_X6_PRESPLIT = 9
 MQ_ENC_OPT_ROWS_PLANES = 10
 MQ_ENC_OPT_LN_FOLD = 11
+MQ_ENC_OPT_CLS_KFREE = 12
 
 
 class MQError(RuntimeError):
@@ -123,6 +124,8 @@ SIGNATURES = {
     "mq_debug_gemm_x6p_ln": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_float, _P]),
     "mq_debug_ln_fold_weight": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "mq_debug_attention": (_I, [_P, _P, _I, _I, _I, _I, ctypes.c_float, _I, _P, _P]),
+    "mq_debug_cls_attention": (_I, [_P, _P, _P, _P, _P, ctypes.c_float, _P, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P,
+                                    _P, _P]),
     "mq_debug_attn_oproj": (_I, [_P, _P, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "mq_debug_int8_screen":(_I, [_P, _P, _I, _P, _P, _P]),
 }
