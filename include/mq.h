@@ -409,6 +409,35 @@ int mq_encoder_read_timing(mq_encoder* enc, float* ms, int n);
 int mq_encoder_embed(mq_encoder* enc, const int32_t* ids, const int32_t* mask, int B, int L,
                      float* out, int io_on_device, void* stream);
 
+/* Cross-encoder scoring (reranking): a BERT cross-encoder is this encoder run on
+ * [CLS] query [SEP] document [SEP] with segment ids, followed by BertPooler and a classifier
+ * (transformers' BertForSequenceClassification; LangChain's CrossEncoderReranker re-orders the
+ * documents of similarity_search(q, k), reference src/agents/nodes.py:93, whose first two the
+ * Grade step reads, src/core/utils.py:64):
+ *   pooled = tanh(Wp h_cls + bp),  logits = Wc pooled + bc
+ * with h_cls the CLS row of the last LayerNorm, NOT L2-normalised.
+ * mq_encoder_load_head uploads the head (host fp32: pooler_w [H][H], pooler_b [H], cls_w
+ * [n_labels][H], cls_b [n_labels]; 1 <= n_labels <= MQ_HEAD_MAX_LABELS, checked before any HIP
+ * call).  It is a separate upload: the blob of mq_encoder_load_weights and
+ * mq_encoder_weight_count do not include it.  Loading again replaces the head; MQ_ESTATE
+ * before mq_encoder_load_weights. */
+#define MQ_HEAD_MAX_LABELS 8
+int mq_encoder_load_head(mq_encoder* enc, const float* pooler_w, const float* pooler_b, const float* cls_w,
+                         const float* cls_b, int n_labels);
+/* ids / types / mask [B, L] int32 -> logits [B, n_labels] f32.  The forward is
+ * mq_encoder_embed's (every path, precision and option of it) with two differences: the
+ * embedding sum takes token-type row types[t], clamped to [0, type_vocab) on the device as the
+ * ids are clamped to the vocabulary, and the tail leaves the CLS rows un-normalised in a
+ * [B, hidden] buffer of the handle; then one launch of cls_head_kernel (K13: fp32 MFMA, fixed
+ * summation order - repeated calls are bit-identical).  All buffers host (io_on_device = 0, the
+ * call synchronises) or all device (asynchronous on `stream`, no allocation once the handle's
+ * buffers have grown to the shape, no host synchronisation).  MQ_ESTATE without a head or when
+ * pooling != MQ_POOL_CLS; B == 0 is a no-op; L <= max_positions.
+ * Scoring always launches eagerly: captured graphs (mq_encoder_set_graphs) stay a feature of
+ * mq_encoder_embed, and no embed graph is ever replayed for a score call. */
+int mq_encoder_score(mq_encoder* enc, const int32_t* ids, const int32_t* types, const int32_t* mask, int B,
+                     int L, float* logits, int io_on_device, void* stream);
+
 /* ------------------------------------------------------------ tokenizer ---- */
 /* Host-side BERT tokenisation (the step Ollama runs before the forward, reference
  * src/medical_engine.py:43).  WordPiece over a local vocab.txt, or the deterministic
@@ -428,6 +457,18 @@ int mq_tokenizer_destroy(mq_tokenizer* tok);
  * returned in *out_len. */
 int mq_tokenizer_encode_batch(mq_tokenizer* tok, const char* const* texts, int n, int pad_to,
                               int32_t* ids, int32_t* mask, int* out_len);
+
+/* Encode n (first, second) text pairs for a cross-encoder: [CLS] A [SEP] B [SEP], types 0
+ * through the first [SEP] and 1 for B and its [SEP]; padding is id 0, type 0, mask 0.  Both the
+ * WordPiece and the char tokenizer.  ids / types / mask hold n * max(max_length, pad_to) int32
+ * and are written [n, L] row-major, L as mq_tokenizer_encode_batch.  Needs max_length >= 5.
+ * A pair longer than max_length is truncated as HF's truncation=True (longest first) truncates
+ * it: with T = max_length - 3, a = |A|, b = |B| - nothing when a + b <= T; else s = the shorter
+ * (the first text when equal): 2 s <= T keeps it whole and cuts the longer to T - s, else the
+ * shorter keeps T / 2 tokens and the longer T - T / 2.  An empty second text is an empty body
+ * that still carries its type-1 [SEP]. */
+int mq_tokenizer_encode_pairs(mq_tokenizer* tok, const char* const* first, const char* const* second, int n,
+                              int pad_to, int32_t* ids, int32_t* types, int32_t* mask, int* out_len);
 
 /* ------------------------------------------------------- testing hooks ---- */
 /* One encoder GEMM on device buffers: out[M,N] = epi(A[M,K] W[N,K]^T + bias (+ resid)),
@@ -502,6 +543,13 @@ int mq_debug_cls_attention(const float* q, const float* x, const float* stats, c
 int mq_debug_attn_oproj(const float* qkv, const int* mask, int B, int L, int H, int heads, float scale,
                         const float* Wo, const float* bo, const float* resid, int cls_only, int hg, int qf,
                         int acc, float* out, void* stream);
+
+/* One launch of the cross-encoder head (K13, cls_head_kernel: the product's kernel, unchanged)
+ * on device buffers: logits [B][n_labels] = cls_w tanh(pooler_w cls_b + pooler_b) + cls_b for
+ * cls [B][H], H 256 / 512 / 768 / 1024, 1 <= n_labels <= MQ_HEAD_MAX_LABELS.  Asynchronous on
+ * `stream`. */
+int mq_debug_cls_head(const float* cls, int B, int H, const float* pooler_w, const float* pooler_b,
+                      const float* cls_w, const float* cls_b, int n_labels, float* logits, void* stream);
 
 /* The int8 screen (K9q) alone for one host query: its kc candidates (screen scores
  * desc, ids; slots past the survivors hold (tau, -1)) and the int8 shadow's statistics

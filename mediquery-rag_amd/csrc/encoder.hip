@@ -5,13 +5,15 @@
 // 12 x [self-attention + FFN] post-LN BERT layers -> CLS (or mean) pool -> L2 norm.
 //
 // Kernels (one forward = 1 + 7*layers + 1 launches):
-//   K1 embed_ln_kernel      word + position + type-0 embedding gather, LayerNorm
+//   K1 embed_ln_kernel      word + position + token-type embedding gather, LayerNorm
 //   K2 gemm (EPI_BIAS)      fused QKV projection          [M,H] x [3H,H]^T
 //   K3 attention_kernel     softmax(QK^T/sqrt(dh) + mask) V, online softmax, LDS tiles
 //   K4 gemm (EPI_RESID)     output projection + bias + residual, then ln_kernel
 //   K5 gemm (EPI_GELU)      FFN up + bias + GELU (erf or tanh)
 //   K6 gemm (EPI_RESID)     FFN down + bias + residual, then ln_kernel
 //   K7 pool_kernel          CLS / masked-mean pooling + L2 normalisation
+// mq_encoder_score runs the same forward with the pairs' segment ids and a tail that leaves the
+// CLS rows un-normalised, then K13 (cls_head.hip): the cross-encoder's pooler + classifier.
 // All GEMMs run on the exact-fp32 MFMA core of gemm_f32.hpp (or its split-f32 form).
 // Few token rows (a single query, B * L <= 64) take forward_rows instead: 5 launches per
 // layer on the K2r / K3r kernels below, LayerNorm applied by the consuming GEMM.
@@ -22,6 +24,7 @@
 #include <memory>
 #include <vector>
 
+#include "cls_head.hpp"
 #include "common.hpp"
 #include "gemm_epi.hpp"
 #include "gemm_f32.hpp"
@@ -554,6 +557,14 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 }
 
 // ------------------------------------------------------- K1 / LayerNorm ------
+// Token-type (segment) row of token `row`: types == nullptr (the embedding forward) is row 0;
+// else the id clamped to [0, type_vocab), as the word ids are - never gather out of bounds.
+__device__ __forceinline__ int type_row(const int* __restrict__ types, int row, int type_vocab) {
+  if (!types) return 0;
+  const int t = types[row];
+  return t < 0 ? 0 : (t >= type_vocab ? type_vocab - 1 : t);
+}
+
 template <int VPL>
 __device__ __forceinline__ void ln_row_store(floatx4 (&x)[VPL], const float* __restrict__ g,
                                              const float* __restrict__ b, float eps,
@@ -586,12 +597,13 @@ __device__ __forceinline__ void ln_row_store(floatx4 (&x)[VPL], const float* __r
 // whole row before writing it, so dst may alias resid row for row (stride H).
 // POOL (the CLS-pooled last layer's FFN-down, MQ_ENC_OPT_CLS_KFREE): the rows are the
 // sequences' CLS rows and this LayerNorm the encoder's last, so the row is L2-normalised here,
-// v / max(||v||, 1e-12) as pool_kernel, and dst is the embedding - no pool launch.
+// v / max(||v||, 1e-12) as pool_kernel, and dst is the embedding - no pool launch.  raw != 0
+// (scoring, mq_encoder_score): the LayerNorm output itself, not normalised.
 template <int VPL, bool POOL = false>
 __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(
     const float* __restrict__ slab, int S, int M, const float* __restrict__ bias,
     const float* resid, int ldr, const float* __restrict__ g, const float* __restrict__ b,
-    float eps, float* dst) {
+    float eps, float* dst, int raw) {
   // one 256-thread block per row (the few-row path has few rows: 4 waves per row keep
   // 4x more slab loads in flight than a wave per row); thread t owns columns t + 256 i
   constexpr int H = VPL * 256;
@@ -651,7 +663,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(
       x[i] = x[i] * rstd * g[c] + b[c];
       ss += x[i] * x[i];
     }
-    const float inv = 1.0f / fmaxf(sqrtf(block_sum(ss)), 1e-12f);
+    const float inv = raw ? 1.0f : 1.0f / fmaxf(sqrtf(block_sum(ss)), 1e-12f);
 #pragma unroll
     for (int i = 0; i < VPL; ++i) dst[(int64_t)row * H + t + 256 * i] = x[i] * inv;
     return;
@@ -834,7 +846,8 @@ __global__ __launch_bounds__(1024) void rows_gemm_kernel(
     const float* __restrict__ W, int ldw, const float* __restrict__ bias,
     const float* __restrict__ resid, int ldr, float* __restrict__ out, int ldo, int64_t o_plane,
     const int* __restrict__ ids, int L, int vocab, const float* __restrict__ pos,
-    const float* __restrict__ typ, int nt_w, float* __restrict__ zbuf, int64_t zn) {
+    const float* __restrict__ typ, const int* __restrict__ types, int type_vocab, int nt_w,
+    float* __restrict__ zbuf, int64_t zn) {
   static_assert(!(LN_IN && (FL & FL_A)), "a LayerNorm input is read row-major");
   static_assert(!((FL & FL_ACC) && (FL & FL_O)), "accumulated output is row-major");
   // zbuf: zn floats (a multiple of 4) this launch zeroes for a LATER launch's FL_ACC adds
@@ -911,16 +924,17 @@ __global__ __launch_bounds__(1024) void rows_gemm_kernel(
 #pragma unroll
         for (int i = 0; i < VPL; ++i) x[rt][i] = floatx4{0.1f * lane, 0.2f, 0.3f, 0.4f * wave};
       } else if constexpr (S_IN == 0) {
-        // layer 0: the row is the embedding sum word[id] + pos[p] + type[0] (as
+        // layer 0: the row is the embedding sum word[id] + pos[p] + type[tt] (as
         // embed_ln_kernel; A = the word table), normalised with the embedding LayerNorm
         int id = ids[rr];
         id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+        const float* trow = typ + (int64_t)type_row(types, rr, type_vocab) * K;
 #pragma unroll
         for (int i = 0; i < VPL; ++i) {
           const int cc = (i * 64 + lane) * 4;
           x[rt][i] = *reinterpret_cast<const floatx4*>(A + (int64_t)id * K + cc) +
                      *reinterpret_cast<const floatx4*>(pos + (int64_t)(rr % L) * K + cc) +
-                     *reinterpret_cast<const floatx4*>(typ + cc);
+                     *reinterpret_cast<const floatx4*>(trow + cc);
         }
       } else {
         // the row is the sum of S_IN split-K planes of the producing GEMM, added in order
@@ -1038,8 +1052,9 @@ __global__ __launch_bounds__(1024) void rows_gemm_kernel(
 template <int VPL>
 __global__ __launch_bounds__(256) void embed_ln_kernel(
     const int* __restrict__ ids, int M, int L, int vocab, const float* __restrict__ word,
-    const float* __restrict__ pos, const float* __restrict__ typ, const float* __restrict__ g,
-    const float* __restrict__ b, float eps, float* __restrict__ out) {
+    const float* __restrict__ pos, const float* __restrict__ typ, const int* __restrict__ types,
+    int type_vocab, const float* __restrict__ g, const float* __restrict__ b, float eps,
+    float* __restrict__ out) {
   constexpr int H = VPL * 256;
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1047,13 +1062,14 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(
   int id = ids[row];
   id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);  // never gather out of bounds
   const int p = row % L;
+  const float* trow = typ + (int64_t)type_row(types, row, type_vocab) * H;
   floatx4 x[VPL];
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
     const int c = (i * 64 + lane) * 4;
     x[i] = *reinterpret_cast<const floatx4*>(word + (int64_t)id * H + c) +
            *reinterpret_cast<const floatx4*>(pos + (int64_t)p * H + c) +
-           *reinterpret_cast<const floatx4*>(typ + c);
+           *reinterpret_cast<const floatx4*>(trow + c);
   }
   ln_row_store<VPL>(x, g, b, eps, out + (int64_t)row * H, lane);
 }
@@ -1640,10 +1656,13 @@ __global__ __launch_bounds__(512) void attn_oproj_rows_kernel(
 
 // --------------------------------------------------------------- K7 pool -----
 // One wave per sequence: CLS row (or masked mean over rows), then x / max(||x||, 1e-12).
+// raw != 0 (one uniform flag of every tail; scoring, mq_encoder_score): the pooled row as it
+// is, the final LayerNorm's output - the cross-encoder head's input.  x * 1.0f is x, so the
+// embedding path's arithmetic is what it was.
 template <int VPL>
 __global__ __launch_bounds__(256) void pool_kernel(const float* __restrict__ hs,
                                                    const int* __restrict__ mask, int B, int L,
-                                                   int pooling, float* __restrict__ out) {
+                                                   int pooling, float* __restrict__ out, int raw) {
   constexpr int H = VPL * 256;
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1671,7 +1690,7 @@ __global__ __launch_bounds__(256) void pool_kernel(const float* __restrict__ hs,
   float ss = 0.f;
 #pragma unroll
   for (int i = 0; i < VPL; ++i) ss += x[i].x * x[i].x + x[i].y * x[i].y + x[i].z * x[i].z + x[i].w * x[i].w;
-  const float inv = 1.0f / fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
+  const float inv = raw ? 1.0f : 1.0f / fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
 #pragma unroll
   for (int i = 0; i < VPL; ++i)
     *reinterpret_cast<floatx4*>(out + (int64_t)b * H + (i * 64 + lane) * 4) = x[i] * inv;
@@ -1687,7 +1706,7 @@ __global__ __launch_bounds__(256) void ln_pool_kernel(const float* __restrict__ 
                                                       int B, int L, int rows, int pooling,
                                                       const float* __restrict__ g,
                                                       const float* __restrict__ be, float eps,
-                                                      float* __restrict__ out) {
+                                                      float* __restrict__ out, int raw) {
   constexpr int H = VPL * 256;
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1729,7 +1748,7 @@ __global__ __launch_bounds__(256) void ln_pool_kernel(const float* __restrict__ 
   float ss = 0.f;
 #pragma unroll
   for (int i = 0; i < VPL; ++i) ss += x[i].x * x[i].x + x[i].y * x[i].y + x[i].z * x[i].z + x[i].w * x[i].w;
-  const float inv = 1.0f / fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
+  const float inv = raw ? 1.0f : 1.0f / fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
 #pragma unroll
   for (int i = 0; i < VPL; ++i)
     *reinterpret_cast<floatx4*>(out + (int64_t)b * H + (i * 64 + lane) * 4) = x[i] * inv;
@@ -2288,6 +2307,12 @@ struct mq_encoder {
   bool cls_kfree = kClsKfreeDefault;  // CLS pooling, batched forward: the last layer without K / V
   Buf wkt;                      // its Wk^T of the last layer [H][H], built at weight load
   Buf cls;                      // its [B] rows: normalised CLS rows, q (H each), u, z (heads H each), live
+  // cross-encoder head (mq_encoder_load_head): Wp [H][H], bp [H], Wc [n_labels][H], bc [n_labels]
+  Buf head;
+  int n_labels = 0;             // 0 = no head loaded
+  Buf cls_state;                // scoring: the raw tail's [B][H] CLS rows, K13's input
+  int* io_types = nullptr;      // staged segment ids of the host-pointer score path
+  size_t io_type_tokens = 0;
   bool use_graphs = false;  // eager measured faster for one query (0.628 vs 0.645 ms: the
                             // graph path stages ids / mask / out through its own buffers)
   uint64_t graph_clock = 0;
@@ -2464,7 +2489,7 @@ void gemm_resid_ln(mq_encoder* e, const GemmArgs& g, const float* lng, const flo
     launch_splitk_gemm(g, S, s);
     e->tl.mark(s, ST_LN);
     hipLaunchKernelGGL((splitk_reduce_ln_kernel<VPL>), dim3((unsigned)g.M), dim3(256), 0, s, g.slab, S,
-                       g.M, g.bias, g.resid, g.ldr, lng, lnb, e->cfg.ln_eps, x);
+                       g.M, g.bias, g.resid, g.ldr, lng, lnb, e->cfg.ln_eps, x, 0);
     return;
   }
   gemm<EPI_RESID>(e, g, stage, s);
@@ -2533,7 +2558,7 @@ void launch_cls_ctx(int B, int L, int H, int heads, float scale, const float* x,
 // slab reduction does all of it; else the GEMM through y (g.out) and ln_pool_kernel.
 template <int VPL>
 void gemm_resid_ln_pool(mq_encoder* e, const GemmArgs& g, const float* lng, const float* lnb, const int* mask,
-                        float* out, int stage, hipStream_t s) {
+                        float* out, int raw, int stage, hipStream_t s) {
   const int H = VPL * 256;
   const int S = splitk_factor(g, e->num_cus, e->splitk_max, e->splitk_tiles);
   if (S && g.ldr == H && g.N == H) {
@@ -2541,13 +2566,13 @@ void gemm_resid_ln_pool(mq_encoder* e, const GemmArgs& g, const float* lng, cons
     launch_splitk_gemm(g, S, s);
     e->tl.mark(s, ST_POOL);
     hipLaunchKernelGGL((splitk_reduce_ln_kernel<VPL, true>), dim3((unsigned)g.M), dim3(256), 0, s, g.slab, S, g.M,
-                       g.bias, g.resid, g.ldr, lng, lnb, e->cfg.ln_eps, out);
+                       g.bias, g.resid, g.ldr, lng, lnb, e->cfg.ln_eps, out, raw);
     return;
   }
   gemm<EPI_RESID>(e, g, stage, s);
   e->tl.mark(s, ST_POOL);
   hipLaunchKernelGGL((ln_pool_kernel<VPL>), dim3((unsigned)((g.M + 3) / 4)), dim3(256), 0, s, g.out, 1, (int64_t)0, mask,
-                     g.M, 1, 1, MQ_POOL_CLS, lng, lnb, e->cfg.ln_eps, out);
+                     g.M, 1, 1, MQ_POOL_CLS, lng, lnb, e->cfg.ln_eps, out, raw);
 }
 
 // One forward.  With CLS pooling the last layer only needs the CLS rows after its
@@ -2558,9 +2583,11 @@ void gemm_resid_ln_pool(mq_encoder* e, const GemmArgs& g, const float* lng, cons
 // FFN-down reduction also applies the closing LayerNorm, the pooling and the L2 norm.  With the
 // option off: K and V for every token ([M, 2H]), attention on the first 32-query tile, the tail
 // on strided views of the activations, and a pool launch.
+// types: the tokens' segment ids (nullptr = all 0, the embedding forward); raw_cls: the tail
+// writes the CLS rows' final LayerNorm output to `out` without the L2 normalisation (scoring).
 template <int VPL>
-int forward_vpl(mq_encoder* e, const int* ids, const int* mask, int B, int L, float* out,
-                hipStream_t s) {
+int forward_vpl(mq_encoder* e, const int* ids, const int* types, const int* mask, int B, int L, float* out,
+                int raw_cls, hipStream_t s) {
   const mq_bert_config& c = e->cfg;
   const int M = B * L, H = c.hidden, F = c.ffn;
   const unsigned row_blocks = (unsigned)((M + 3) / 4);
@@ -2568,7 +2595,7 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* mask, int B, int L, fl
   const int q_tiles = (L + 31) / 32;
   e->tl.mark(s, ST_EMBED);
   hipLaunchKernelGGL((embed_ln_kernel<VPL>), dim3(row_blocks), dim3(256), 0, s, ids, M, L,
-                     c.vocab_size, e->word, e->pos, e->typ, e->eg, e->eb, c.ln_eps, e->x.p);
+                     c.vocab_size, e->word, e->pos, e->typ, types, c.type_vocab, e->eg, e->eb, c.ln_eps, e->x.p);
   // LayerNorm deferred into the consumers (LnArgs) on the full-M layers: exact f32, rows
   // enough for the tiled path, hidden a whole number of kLnPartW-column partials
   const int nt = H / kLnPartW;
@@ -2769,7 +2796,7 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* mask, int B, int L, fl
       launch_gemm_stats(down, stats_out(st2), e->num_cus, s);
       y_pending = true;
     } else if (kfree) {  // the encoder's end: LN2, CLS pooling and the L2 norm with the reduction
-      gemm_resid_ln_pool<VPL>(e, down, w.ln2g, w.ln2b, mask, out, ST_FFN_DOWN, s);
+      gemm_resid_ln_pool<VPL>(e, down, w.ln2g, w.ln2b, mask, out, raw_cls, ST_FFN_DOWN, s);
       pooled = true;
     } else {
       gemm_resid_ln<VPL>(e, down, w.ln2g, w.ln2b, e->x.p, ST_FFN_DOWN, s);
@@ -2780,7 +2807,7 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* mask, int B, int L, fl
     e->tl.mark(s, ST_POOL);
     const bool pruned = c.pooling == MQ_POOL_CLS;  // x holds [B, H] CLS rows
     hipLaunchKernelGGL((pool_kernel<VPL>), dim3((B + 3) / 4), dim3(256), 0, s, e->x.p, mask, B,
-                       pruned ? 1 : L, c.pooling, out);
+                       pruned ? 1 : L, c.pooling, out, raw_cls);
   }
   e->tl.close(s);
   MQ_HIP(hipGetLastError());
@@ -2807,6 +2834,8 @@ struct RowsArgs {
   int L = 1, vocab = 0;
   const float* pos = nullptr;
   const float* typ = nullptr;
+  const int* types = nullptr;  // segment ids (nullptr = type row 0)
+  int type_vocab = 1;
   int nt_w = 0;  // weights loaded non-temporally (layers past resident_layers)
   float* zbuf = nullptr;  // zn floats this launch zeroes for a later launch's FL_ACC adds
   int64_t zn = 0;
@@ -2823,7 +2852,8 @@ void launch_rows_rt(const RowsArgs& g, const float* lng, const float* lnb, float
   hipLaunchKernelGGL((rows_gemm_kernel<EPI, LN_IN, VPL, NB, S_IN, RT, FL>),
                      dim3(g.N / kRT, (g.M + kRT * RT - 1) / (kRT * RT), g.splits), dim3(64 * kRWaves), 0, s,
                      g.A, g.lda, g.a_plane, g.M, lng, lnb, eps, ln_out, g.W, g.ldw, g.bias, g.resid, g.ldr,
-                     g.out, g.ldo, g.o_plane, g.ids, g.L, g.vocab, g.pos, g.typ, g.nt_w, g.zbuf, g.zn);
+                     g.out, g.ldo, g.o_plane, g.ids, g.L, g.vocab, g.pos, g.typ, g.types, g.type_vocab, g.nt_w, g.zbuf,
+                     g.zn);
 }
 
 template <int EPI, bool LN_IN, int VPL, int NB, int S_IN, int FL = 0>
@@ -2947,8 +2977,8 @@ int oproj_heads_per_plane(const mq_encoder* e, int L) {
 // and ln_pool applies the last LN2 to the pooled rows.  The CLS-only last layer carries
 // the B CLS rows past attention as forward_vpl does.
 template <int VPL>
-int forward_rows(mq_encoder* e, const int* ids, const int* mask, int B, int L, float* out,
-                 hipStream_t s) {
+int forward_rows(mq_encoder* e, const int* ids, const int* types, const int* mask, int B, int L, float* out,
+                 int raw, hipStream_t s) {
   const mq_bert_config& c = e->cfg;
   const int M = B * L, H = c.hidden, F = c.ffn;
   const float eps = c.ln_eps;
@@ -2981,6 +3011,8 @@ int forward_rows(mq_encoder* e, const int* ids, const int* mask, int B, int L, f
       qkv.vocab = c.vocab_size;
       qkv.pos = e->pos;
       qkv.typ = e->typ;
+      qkv.types = types;
+      qkv.type_vocab = c.type_vocab;
     }
     const LayerW* pl = li ? &e->layers[li - 1] : nullptr;
     const float* lg = pl ? pl->ln2g : e->eg;
@@ -3041,7 +3073,7 @@ int forward_rows(mq_encoder* e, const int* ids, const int* mask, int B, int L, f
   const LayerW& last = e->layers.back();
   const int pool_rows = c.pooling == MQ_POOL_CLS ? 1 : L;  // slab holds [B, H] CLS rows or [M, H]
   hipLaunchKernelGGL((ln_pool_kernel<VPL>), dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, e->slab.p, dacc ? 1 : dsplit,
-                     (int64_t)prev_rows * H, mask, B, L, pool_rows, c.pooling, last.ln2g, last.ln2b, eps, out);
+                     (int64_t)prev_rows * H, mask, B, L, pool_rows, c.pooling, last.ln2g, last.ln2b, eps, out, raw);
   e->tl.close(s);
   MQ_HIP(hipGetLastError());
   return MQ_OK;
@@ -3062,14 +3094,21 @@ bool use_rows_path(const mq_encoder* e, int B, int L) {
 
 namespace {
 
-int forward(mq_encoder* e, const int* ids, const int* mask, int B, int L, float* out,
-            hipStream_t s) {
+// The one forward of both entry points: mq_encoder_embed passes types = nullptr, raw = 0;
+// mq_encoder_score the segment ids and raw = 1 (out = the handle's [B][H] CLS-state buffer).
+int forward(mq_encoder* e, const int* ids, const int* types, const int* mask, int B, int L, float* out,
+            int raw, hipStream_t s) {
   const bool rows = use_rows_path(e, B, L);
+  auto go = [&](auto vpl) {
+    constexpr int VPL = decltype(vpl)::value;
+    return rows ? forward_rows<VPL>(e, ids, types, mask, B, L, out, raw, s)
+                : forward_vpl<VPL>(e, ids, types, mask, B, L, out, raw, s);
+  };
   switch (e->cfg.hidden) {
-    case 256: return rows ? forward_rows<1>(e, ids, mask, B, L, out, s) : forward_vpl<1>(e, ids, mask, B, L, out, s);
-    case 512: return rows ? forward_rows<2>(e, ids, mask, B, L, out, s) : forward_vpl<2>(e, ids, mask, B, L, out, s);
-    case 768: return rows ? forward_rows<3>(e, ids, mask, B, L, out, s) : forward_vpl<3>(e, ids, mask, B, L, out, s);
-    default: return rows ? forward_rows<4>(e, ids, mask, B, L, out, s) : forward_vpl<4>(e, ids, mask, B, L, out, s);
+    case 256: return go(IC<1>{});
+    case 512: return go(IC<2>{});
+    case 768: return go(IC<3>{});
+    default: return go(IC<4>{});
   }
 }
 
@@ -3104,7 +3143,7 @@ int launch_graph(mq_encoder* e, int B, int L, hipStream_t s) {
     }
     hipGraph_t graph = nullptr;
     MQ_HIP(hipStreamBeginCapture(e->cap_stream, hipStreamCaptureModeThreadLocal));
-    const int rc = forward(e, e->io_ids, e->io_mask, B, L, e->io_out.p, e->cap_stream);
+    const int rc = forward(e, e->io_ids, nullptr, e->io_mask, B, L, e->io_out.p, 0, e->cap_stream);
     const hipError_t end = hipStreamEndCapture(e->cap_stream, &graph);
     if (rc) {
       if (graph) (void)hipGraphDestroy(graph);
@@ -3185,8 +3224,9 @@ int mq_encoder_destroy(mq_encoder* e) {
   {
     DeviceGuard dg(e->device);
     for (Buf* b : {&e->weights, &e->x, &e->y, &e->qkv, &e->ctx, &e->ffn, &e->io_out, &e->slab, &e->w3, &e->wfrag,
-                   &e->lnst, &e->wkt, &e->cls})
+                   &e->lnst, &e->wkt, &e->cls, &e->head, &e->cls_state})
       b->release();
+    if (e->io_types) (void)hipFree(e->io_types);
     if (e->io_ids) (void)hipFree(e->io_ids);
     if (e->io_mask) (void)hipFree(e->io_mask);
     e->pin.release();
@@ -3515,19 +3555,12 @@ int mq_encoder_read_timing(mq_encoder* e, float* ms, int n) {
   return MQ_OK;
 }
 
-int mq_encoder_embed(mq_encoder* e, const int32_t* ids, const int32_t* mask, int B, int L,
-                     float* out, int io_on_device, void* stream) {
-  clear_error();
-  MQ_CHECK_ARG(e, "NULL encoder");
-  MQ_CHECK_ARG(B >= 0 && L >= 1, "bad shape B=%d L=%d", B, L);
-  MQ_CHECK_ARG(L <= e->cfg.max_positions, "L=%d exceeds max_positions %d", L, e->cfg.max_positions);
-  if (B == 0) return MQ_OK;
-  MQ_CHECK_ARG(ids && mask && out, "NULL buffer");
-  MQ_CHECK_ARG((int64_t)B * L < (1ll << 31) / 4096, "batch too large");
-  if (!e->loaded) MQ_FAIL(MQ_ESTATE, "encoder weights not loaded");
-  std::lock_guard<std::mutex> lk(e->mu);
-  DeviceGuard dg(e->device);
-  hipStream_t s = (hipStream_t)stream;
+}  // extern "C"
+
+namespace {
+
+// The activation buffers of one forward of B x L tokens (grown on demand, never shrunk).
+int ensure_forward_bufs(mq_encoder* e, int B, int L) {
   const mq_bert_config& c = e->cfg;
   const size_t M = (size_t)B * L;
   if (e->tl.used > 4096) e->tl.drain();  // bound the event pool while timing
@@ -3549,22 +3582,51 @@ int mq_encoder_embed(mq_encoder* e, const int32_t* ids, const int32_t* mask, int
     rc = bn.first->ensure(bn.second);
     if (rc) return rc;
   }
+  return MQ_OK;
+}
+
+// The handle's own io buffers for M tokens and B output rows of `hidden` floats.
+int ensure_io(mq_encoder* e, size_t M, int B) {
+  if (e->io_tokens < M) {
+    if (e->io_ids) (void)hipFree(e->io_ids);
+    if (e->io_mask) (void)hipFree(e->io_mask);
+    e->io_ids = e->io_mask = nullptr;
+    e->io_tokens = 0;
+    if (hipMalloc((void**)&e->io_ids, M * 4) != hipSuccess ||
+        hipMalloc((void**)&e->io_mask, M * 4) != hipSuccess)
+      MQ_FAIL(MQ_ENOMEM, "hipMalloc(io) failed");
+    e->io_tokens = M;
+  }
+  return e->io_out.ensure((size_t)B * e->cfg.hidden);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mq_encoder_embed(mq_encoder* e, const int32_t* ids, const int32_t* mask, int B, int L,
+                     float* out, int io_on_device, void* stream) {
+  clear_error();
+  MQ_CHECK_ARG(e, "NULL encoder");
+  MQ_CHECK_ARG(B >= 0 && L >= 1, "bad shape B=%d L=%d", B, L);
+  MQ_CHECK_ARG(L <= e->cfg.max_positions, "L=%d exceeds max_positions %d", L, e->cfg.max_positions);
+  if (B == 0) return MQ_OK;
+  MQ_CHECK_ARG(ids && mask && out, "NULL buffer");
+  MQ_CHECK_ARG((int64_t)B * L < (1ll << 31) / 4096, "batch too large");
+  if (!e->loaded) MQ_FAIL(MQ_ESTATE, "encoder weights not loaded");
+  std::lock_guard<std::mutex> lk(e->mu);
+  DeviceGuard dg(e->device);
+  hipStream_t s = (hipStream_t)stream;
+  const mq_bert_config& c = e->cfg;
+  const size_t M = (size_t)B * L;
+  int rc = ensure_forward_bufs(e, B, L);
+  if (rc) return rc;
   const bool graph = e->use_graphs && !e->tl.on;
   const int* dids = ids;
   const int* dmask = mask;
   float* dout = out;
   if (!io_on_device || graph) {  // stage through the encoder's own io buffers
-    if (e->io_tokens < M) {
-      if (e->io_ids) (void)hipFree(e->io_ids);
-      if (e->io_mask) (void)hipFree(e->io_mask);
-      e->io_ids = e->io_mask = nullptr;
-      e->io_tokens = 0;
-      if (hipMalloc((void**)&e->io_ids, M * 4) != hipSuccess ||
-          hipMalloc((void**)&e->io_mask, M * 4) != hipSuccess)
-        MQ_FAIL(MQ_ENOMEM, "hipMalloc(io) failed");
-      e->io_tokens = M;
-    }
-    rc = e->io_out.ensure((size_t)B * c.hidden);
+    rc = ensure_io(e, M, B);
     if (rc) return rc;
     const hipMemcpyKind kind = io_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (!io_on_device && M * 8 + (size_t)B * c.hidden * 4 <= (1u << 20)) {
@@ -3586,7 +3648,7 @@ int mq_encoder_embed(mq_encoder* e, const int32_t* ids, const int32_t* mask, int
   if (graph) {
     rc = launch_graph(e, B, L, s);
   } else {
-    rc = forward(e, dids, dmask, B, L, dout, s);
+    rc = forward(e, dids, nullptr, dmask, B, L, dout, 0, s);
   }
   if (rc) return rc;
   if (io_on_device && dout != out)
@@ -3602,6 +3664,97 @@ int mq_encoder_embed(mq_encoder* e, const int32_t* ids, const int32_t* mask, int
       MQ_HIP(hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, s));
       MQ_HIP(hipStreamSynchronize(s));
     }
+  }
+  return MQ_OK;
+}
+
+int mq_encoder_load_head(mq_encoder* e, const float* pooler_w, const float* pooler_b, const float* cls_w,
+                         const float* cls_b, int n_labels) {
+  clear_error();
+  MQ_CHECK_ARG(n_labels >= 1 && n_labels <= MQ_HEAD_MAX_LABELS, "n_labels must be in [1, %d] (got %d)",
+               MQ_HEAD_MAX_LABELS, n_labels);
+  MQ_CHECK_ARG(e, "NULL encoder");
+  MQ_CHECK_ARG(pooler_w && pooler_b && cls_w && cls_b, "NULL argument");
+  if (!e->loaded) MQ_FAIL(MQ_ESTATE, "encoder weights not loaded");
+  std::lock_guard<std::mutex> lk(e->mu);
+  DeviceGuard dg(e->device);
+  const size_t H = (size_t)e->cfg.hidden;
+  e->n_labels = 0;  // (no half-replaced head after a failure)
+  const int rc = e->head.ensure(H * H + H + (size_t)MQ_HEAD_MAX_LABELS * (H + 1));
+  if (rc) return rc;
+  float* p = e->head.p;
+  MQ_HIP(hipMemcpy(p, pooler_w, H * H * 4, hipMemcpyHostToDevice));
+  MQ_HIP(hipMemcpy(p + H * H, pooler_b, H * 4, hipMemcpyHostToDevice));
+  MQ_HIP(hipMemcpy(p + H * H + H, cls_w, (size_t)n_labels * H * 4, hipMemcpyHostToDevice));
+  MQ_HIP(hipMemcpy(p + H * H + H + (size_t)MQ_HEAD_MAX_LABELS * H, cls_b, (size_t)n_labels * 4, hipMemcpyHostToDevice));
+  e->n_labels = n_labels;
+  return MQ_OK;
+}
+
+int mq_encoder_score(mq_encoder* e, const int32_t* ids, const int32_t* types, const int32_t* mask, int B, int L,
+                     float* logits, int io_on_device, void* stream) {
+  clear_error();
+  MQ_CHECK_ARG(e, "NULL encoder");
+  MQ_CHECK_ARG(B >= 0 && L >= 1, "bad shape B=%d L=%d", B, L);
+  MQ_CHECK_ARG(L <= e->cfg.max_positions, "L=%d exceeds max_positions %d", L, e->cfg.max_positions);
+  if (!e->loaded) MQ_FAIL(MQ_ESTATE, "encoder weights not loaded");
+  if (e->cfg.pooling != MQ_POOL_CLS) MQ_FAIL(MQ_ESTATE, "scoring needs CLS pooling (the head reads the CLS state)");
+  if (B == 0) return MQ_OK;
+  MQ_CHECK_ARG(ids && types && mask && logits, "NULL buffer");
+  MQ_CHECK_ARG((int64_t)B * L < (1ll << 31) / 4096, "batch too large");
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (e->n_labels < 1) MQ_FAIL(MQ_ESTATE, "no cross-encoder head loaded (mq_encoder_load_head)");
+  DeviceGuard dg(e->device);
+  hipStream_t s = (hipStream_t)stream;
+  const mq_bert_config& c = e->cfg;
+  const size_t M = (size_t)B * L, H = (size_t)c.hidden, nl = (size_t)e->n_labels;
+  int rc = ensure_forward_bufs(e, B, L);
+  if (!rc) rc = e->cls_state.ensure((size_t)B * H);
+  if (rc) return rc;
+  const int* dids = ids;
+  const int* dtypes = types;
+  const int* dmask = mask;
+  float* dlogits = logits;
+  // host io: ids | types | mask | logits through one pinned block, one DMA each way per array
+  const size_t ob = (size_t)B * nl * 4;
+  if (!io_on_device) {
+    rc = ensure_io(e, M, B);  // (io_out's B x hidden floats hold the B x n_labels logits)
+    if (rc) return rc;
+    if (e->io_type_tokens < M) {
+      if (e->io_types) (void)hipFree(e->io_types);
+      e->io_types = nullptr;
+      e->io_type_tokens = 0;
+      if (hipMalloc((void**)&e->io_types, M * 4) != hipSuccess) MQ_FAIL(MQ_ENOMEM, "hipMalloc(io) failed");
+      e->io_type_tokens = M;
+    }
+    rc = e->pin.ensure(M * 12 + ob);
+    if (rc) return rc;
+    unsigned char* hp = e->pin.as<unsigned char>();
+    memcpy(hp, ids, M * 4);
+    memcpy(hp + M * 4, types, M * 4);
+    memcpy(hp + M * 8, mask, M * 4);
+    MQ_HIP(hipMemcpyAsync(e->io_ids, hp, M * 4, hipMemcpyHostToDevice, s));
+    MQ_HIP(hipMemcpyAsync(e->io_types, hp + M * 4, M * 4, hipMemcpyHostToDevice, s));
+    MQ_HIP(hipMemcpyAsync(e->io_mask, hp + M * 8, M * 4, hipMemcpyHostToDevice, s));
+    dids = e->io_ids;
+    dtypes = e->io_types;
+    dmask = e->io_mask;
+    dlogits = e->io_out.p;
+  }
+  // always eager: captured graphs are the embedding forward's (launch_graph), never replayed here
+  rc = forward(e, dids, dtypes, dmask, B, L, e->cls_state.p, 1, s);
+  if (rc) return rc;
+  const float* hp = e->head.p;
+  e->tl.mark(s, ST_POOL);
+  launch_cls_head(e->cls_state.p, B, c.hidden, hp, hp + H * H, hp + H * H + H,
+                  hp + H * H + H + (size_t)MQ_HEAD_MAX_LABELS * H, e->n_labels, dlogits, s);
+  e->tl.close(s);
+  MQ_HIP(hipGetLastError());
+  if (!io_on_device) {
+    unsigned char* out_pin = e->pin.as<unsigned char>() + M * 12;
+    MQ_HIP(hipMemcpyAsync(out_pin, dlogits, ob, hipMemcpyDeviceToHost, s));
+    MQ_HIP(hipStreamSynchronize(s));
+    memcpy(logits, out_pin, ob);
   }
   return MQ_OK;
 }

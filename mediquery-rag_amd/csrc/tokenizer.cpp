@@ -285,13 +285,46 @@ struct mq_tokenizer {
     }
   }
 
-  std::vector<int> encode(const char* text) const {
+  std::vector<int> body_ids(const char* text) const {
     const std::vector<uint32_t> cps = decode_utf8(text ? text : "");
     std::vector<int> body;
     if (wordpiece)
       wordpiece_ids(cps, body);
     else
       char_ids(cps, body);
+    return body;
+  }
+
+  // [CLS] A [SEP] B [SEP] of a text pair, cut to max_length longest-first (mq.h); n_first =
+  // the tokens through the first [SEP] (segment 0)
+  std::vector<int> encode_pair(const char* first, const char* second, int& n_first) const {
+    const std::vector<int> A = body_ids(first), B = body_ids(second);
+    const size_t T = (size_t)std::max(0, max_length - 3);
+    size_t a = A.size(), b = B.size();
+    if (a + b > T) {
+      const bool first_short = a <= b;
+      size_t& sh = first_short ? a : b;
+      size_t& lo = first_short ? b : a;
+      if (2 * sh <= T) {
+        lo = T - sh;
+      } else {
+        sh = T / 2;
+        lo = T - T / 2;
+      }
+    }
+    std::vector<int> seq;
+    seq.reserve(a + b + 3);
+    seq.push_back(cls);
+    seq.insert(seq.end(), A.begin(), A.begin() + a);
+    seq.push_back(sep);
+    n_first = (int)seq.size();
+    seq.insert(seq.end(), B.begin(), B.begin() + b);
+    seq.push_back(sep);
+    return seq;
+  }
+
+  std::vector<int> encode(const char* text) const {
+    const std::vector<int> body = body_ids(text);
     const size_t keep = std::min<size_t>(body.size(), (size_t)std::max(0, max_length - 2));
     std::vector<int> seq;
     seq.reserve(keep + 2);
@@ -414,6 +447,41 @@ int mq_tokenizer_encode_batch(mq_tokenizer* t, const char* const* texts, int n, 
     const int len = (int)seqs[i].size();
     for (int j = 0; j < L; ++j) {
       row[j] = j < len ? seqs[i][j] : kPad;
+      mrow[j] = j < len ? 1 : 0;
+    }
+  }
+  *out_len = L;
+  return MQ_OK;
+}
+
+int mq_tokenizer_encode_pairs(mq_tokenizer* t, const char* const* first, const char* const* second, int n,
+                              int pad_to, int32_t* ids, int32_t* types, int32_t* mask, int* out_len) {
+  mq::clear_error();
+  if (!t || n < 0 || !out_len || (n > 0 && (!first || !second || !ids || !types || !mask))) {
+    mq::set_error("bad encode_pairs arguments");
+    return MQ_EINVAL;
+  }
+  if (t->max_length < 5) {
+    mq::set_error("encode_pairs needs max_length >= 5 (got %d)", t->max_length);
+    return MQ_EINVAL;
+  }
+  std::vector<std::vector<int>> seqs((size_t)n);
+  std::vector<int> nfirst((size_t)n, 0);
+  int L = 0;
+  for (int i = 0; i < n; ++i) {
+    seqs[i] = t->encode_pair(first[i], second[i], nfirst[i]);
+    L = std::max<int>(L, (int)seqs[i].size());
+  }
+  L = std::max(L, std::min(pad_to, t->max_length));
+  if (pad_to > t->max_length) L = std::max(L, pad_to);
+  for (int i = 0; i < n; ++i) {
+    int32_t* row = ids + (size_t)i * L;
+    int32_t* trow = types + (size_t)i * L;
+    int32_t* mrow = mask + (size_t)i * L;
+    const int len = (int)seqs[i].size();
+    for (int j = 0; j < L; ++j) {
+      row[j] = j < len ? seqs[i][j] : kPad;
+      trow[j] = j < len && j >= nfirst[i] ? 1 : 0;
       mrow[j] = j < len ? 1 : 0;
     }
   }

@@ -3,6 +3,8 @@
 Drop-in replacements for the reference's retrieval pair:
     OllamaEmbeddings("shaw/dmeta-embedding-zh")  ->  HipBertEmbeddings
     langchain_chroma.Chroma                        ->  HipChroma
+and, over what a search returns, LangChain's cross-encoder reranking:
+    HuggingFaceCrossEncoder / CrossEncoderReranker ->  HipCrossEncoder / HipReranker
 backed by libmqhip.so (hand-written HIP for gfx950, C ABI in include/mq.h).
 """
 from .config import BertConfig, DMETA_BASE, GELU_ERF, GELU_TANH, POOL_CLS, POOL_MEAN
@@ -11,6 +13,7 @@ from ._lib import MQError, MQ_MAX_K, device_count, lib
 from .native import Encoder, FlatIndex, merge_topk_device, merge_topk_host
 from .embeddings import HipBertEmbeddings
 from .vectorstore import HipChroma
+from .cross_encoder import HipCrossEncoder, HipReranker
 
 # LangChain-compatible aliases for a one-line swap at src/medical_engine.py:25-26
 OllamaEmbeddings = HipBertEmbeddings
@@ -19,4 +22,4 @@ Chroma = HipChroma
 __all__ = ["BertConfig", "DMETA_BASE", "GELU_ERF", "GELU_TANH", "POOL_CLS", "POOL_MEAN",
            "Document", "HAVE_LANGCHAIN", "MQError", "MQ_MAX_K", "device_count", "lib", "Encoder",
            "FlatIndex", "merge_topk_device", "merge_topk_host", "HipBertEmbeddings", "HipChroma",
-           "OllamaEmbeddings", "Chroma"]
+           "OllamaEmbeddings", "Chroma", "HipCrossEncoder", "HipReranker"]

@@ -21,6 +21,7 @@ MQ_DTYPE_F32, MQ_DTYPE_BF16, MQ_DTYPE_F32X6, MQ_DTYPE_F32_SCREEN = 0, 1, 2, 3
 MQ_GELU_ERF, MQ_GELU_TANH = 0, 1
 MQ_POOL_CLS, MQ_POOL_MEAN = 0, 1
 MQ_MAX_K = 64
+MQ_HEAD_MAX_LABELS = 8           # most labels a cross-encoder head carries (mq_encoder_load_head)
 MQ_MASK_SET, MQ_MASK_AND, MQ_MASK_OR, MQ_MASK_CLEAR = 0, 1, 2, 3
 MQ_CONTAINS_MAX_BYTES = 256      # longest mq_mask_contains pattern (UTF-8 bytes)
 MQ_CONTAINS_SPAN_BYTES = 16384   # text bytes one workgroup of the scan owns
@@ -111,12 +112,17 @@ SIGNATURES = {
     "mq_encoder_set_timing": (_I, [_P, _I]),
     "mq_encoder_read_timing": (_I, [_P, _P, _I]),
     "mq_encoder_embed": (_I, [_P, _P, _P, _I, _I, _P, _I, _P]),
+    "mq_encoder_load_head": (_I, [_P, _P, _P, _P, _P, _I]),
+    "mq_encoder_score": (_I, [_P, _P, _P, _P, _I, _I, _P, _I, _P]),
     "mq_tokenizer_create_wordpiece": (_I, [ctypes.c_char_p, _I, _I, _PP]),
     "mq_tokenizer_create_wordpiece_tokens": (_I, [ctypes.POINTER(ctypes.c_char_p), _I, _I, _I, _PP]),
     "mq_tokenizer_create_char": (_I, [_I, _I, _PP]),
     "mq_tokenizer_destroy": (_I, [_P]),
     "mq_tokenizer_encode_batch": (_I, [_P, ctypes.POINTER(ctypes.c_char_p), _I, _I, _P, _P,
                                        ctypes.POINTER(_I)]),
+    "mq_tokenizer_encode_pairs": (_I, [_P, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_char_p), _I, _I,
+                                       _P, _P, _P, ctypes.POINTER(_I)]),
+    "mq_debug_cls_head": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _P, _P]),
     "mq_debug_gemm_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "mq_debug_w3_bytes": (_I64, [_I, _I]),
     "mq_debug_split_w3": (_I, [_P, _I, _I, _P, _P]),

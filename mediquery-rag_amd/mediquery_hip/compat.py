@@ -77,3 +77,29 @@ except Exception:
                 get_relevant_documents = invoke
 
             return _Retriever()
+
+
+# Cross-encoder reranking (langchain_community.cross_encoders.BaseCrossEncoder,
+# langchain_core.documents.BaseDocumentCompressor): the real classes when importable, else
+# stand-ins with the same surface.
+try:  # pragma: no cover - exercised only where langchain is installed
+    from langchain_community.cross_encoders import BaseCrossEncoder as CrossEncoderBase  # type: ignore
+except Exception:
+    class CrossEncoderBase:
+        def score(self, text_pairs):
+            raise NotImplementedError
+
+try:  # pragma: no cover
+    from langchain_core.documents import BaseDocumentCompressor as _PydanticCompressor  # type: ignore
+
+    class DocumentCompressorBase(_PydanticCompressor):
+        """LangChain's compressor base (a pydantic model) accepting plain attributes."""
+        model_config = {"arbitrary_types_allowed": True, "extra": "allow"}
+except Exception:
+    class DocumentCompressorBase:
+        def compress_documents(self, documents, query, callbacks=None):
+            raise NotImplementedError
+
+        async def acompress_documents(self, documents, query, callbacks=None):
+            return await asyncio.get_running_loop().run_in_executor(
+                None, self.compress_documents, documents, query, callbacks)

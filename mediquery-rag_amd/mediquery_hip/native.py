@@ -7,7 +7,7 @@ import numpy as np
 
 from . import _lib
 from .config import BertConfig
-from .weights import state_dict_to_blob, synthetic_state_dict
+from .weights import head_from_state_dict, state_dict_to_blob, synthetic_state_dict
 
 
 class FlatIndex:
@@ -256,7 +256,8 @@ def merge_topk_device(scores, ids, k_out, out_scores, out_ids, stream=None):
 
 class Encoder:
     """BERT encoder on one GPU (K1..K7).  `weights`: HF-named state dict, or None for
-    the seeded synthetic weights of `cfg` (see weights.py)."""
+    the seeded synthetic weights of `cfg` (see weights.py).  A cross-encoder head is a
+    separate upload (`load_head`); without one `score` raises."""
 
     def __init__(self, cfg: BertConfig, weights=None, seed=0, device=0):
         self.cfg = cfg
@@ -271,6 +272,7 @@ class Encoder:
         if n != blob.size:
             raise ValueError("weight blob %d floats, library expects %d" % (blob.size, n))
         _lib.call("mq_encoder_load_weights", self._h, _lib.ptr(blob), blob.size)
+        self.n_labels = 0
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None
@@ -342,6 +344,42 @@ class Encoder:
         B, L = ids.shape
         _lib.call("mq_encoder_embed", self._h, _lib.ptr(ids), _lib.ptr(mask), B, L, _lib.ptr(out),
                   1, _lib.stream_handle(stream))
+
+    def load_head(self, sd):
+        """Upload a cross-encoder head (mq_encoder_load_head): `sd` holds pooler.dense.* and
+        classifier.* (weights.HEAD_NAMES); n_labels = classifier.weight's rows, 1..8, checked
+        here before any HIP call.  Loading again replaces the head."""
+        pw, pb, cw, cb = head_from_state_dict(sd, self.cfg)
+        n_labels = int(cw.shape[0])
+        if not 1 <= n_labels <= _lib.MQ_HEAD_MAX_LABELS:
+            raise ValueError("n_labels must be in [1, %d] (got %d)" % (_lib.MQ_HEAD_MAX_LABELS, n_labels))
+        _lib.call("mq_encoder_load_head", self._h, _lib.ptr(pw), _lib.ptr(pb), _lib.ptr(cw), _lib.ptr(cb), n_labels)
+        self.n_labels = n_labels
+
+    def score(self, ids, types, mask):
+        """Cross-encoder logits float32 [B, n_labels] of token pairs: ids / types (segment
+        ids) / mask int [B, L] host arrays (mq_encoder_score)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        types = np.ascontiguousarray(types, dtype=np.int32)
+        mask = np.ascontiguousarray(mask, dtype=np.int32)
+        if types.shape != ids.shape or mask.shape != ids.shape or ids.ndim != 2:
+            raise ValueError("ids, types and mask must share one [B, L] shape")
+        B, L = ids.shape
+        out = np.empty((B, max(1, self.n_labels)), dtype=np.float32)
+        _lib.call("mq_encoder_score", self._h, _lib.ptr(ids), _lib.ptr(types), _lib.ptr(mask), B, L,
+                  _lib.ptr(out), 0, None)
+        return out
+
+    def score_device(self, ids, types, mask, out, stream=None):
+        """ids / types / mask int32 [B, L], out f32 [B, n_labels] - contiguous torch device
+        tensors; asynchronous on the given (or current) torch stream."""
+        if tuple(types.shape) != tuple(ids.shape) or tuple(mask.shape) != tuple(ids.shape):
+            raise ValueError("ids, types and mask must share one [B, L] shape")
+        B, L = ids.shape
+        if out.numel() < B * max(1, self.n_labels):
+            raise ValueError("out holds %d floats, needs B * n_labels = %d" % (out.numel(), B * self.n_labels))
+        _lib.call("mq_encoder_score", self._h, _lib.ptr(ids), _lib.ptr(types), _lib.ptr(mask), B, L,
+                  _lib.ptr(out), 1, _lib.stream_handle(stream))
 
 
 def check_mask_words(bits, n, device=None):

@@ -35,7 +35,51 @@ def _pack(seqs, max_length, pad_to=None):
     return ids, mask
 
 
-class CharTokenizer:
+def pair_budget(a, b, max_length):
+    """Tokens kept of a pair's two bodies (lengths a, b) under [CLS] A [SEP] B [SEP] <=
+    max_length: HF's truncation=True (longest first) as `tokenizers` computes it."""
+    T = max_length - 3
+    if a + b <= T:
+        return a, b
+    s = min(a, b)
+    if 2 * s <= T:
+        short, long_ = s, T - s
+    else:
+        short, long_ = T // 2, T - T // 2
+    return (short, long_) if a <= b else (long_, short)
+
+
+def _pack_pairs(pairs, max_length, pad_to=None):
+    """List of (seq, n_first) -> (ids, types, mask) int32 [n, L], right padded; types are 0
+    through the first [SEP] (n_first tokens) and 1 for the second text and its [SEP]."""
+    ids, mask = _pack([s for s, _ in pairs], max_length, pad_to)
+    types = np.zeros_like(ids)
+    for i, (s, n_first) in enumerate(pairs):
+        types[i, n_first:len(s)] = 1
+    return ids, types, mask
+
+
+class _PairMixin:
+    """`tok.pairs(firsts, seconds, pad_to=None) -> (ids, types, mask)` for a tokenizer with
+    `body(text)`, cls / sep ids and max_length (>= 5): the cross-encoder framing of
+    mq_tokenizer_encode_pairs (include/mq.h)."""
+
+    def encode_pair(self, first, second):
+        if self.max_length < 5:
+            raise ValueError("pairs need max_length >= 5 (got %d)" % self.max_length)
+        A, B = self.body(first), self.body(second)
+        a, b = pair_budget(len(A), len(B), self.max_length)
+        cls, sep = getattr(self, "cls", CLS), getattr(self, "sep", SEP)
+        return [cls] + A[:a] + [sep] + B[:b] + [sep], a + 2
+
+    def pairs(self, firsts, seconds, pad_to=None):
+        firsts, seconds = list(firsts), list(seconds)
+        if len(firsts) != len(seconds):
+            raise ValueError("pairs: %d first texts, %d second texts" % (len(firsts), len(seconds)))
+        return _pack_pairs([self.encode_pair(f, s) for f, s in zip(firsts, seconds)], self.max_length, pad_to)
+
+
+class CharTokenizer(_PairMixin):
     def __init__(self, vocab_size=21128, max_length=512):
         self.vocab_size = vocab_size
         self.max_length = max_length
@@ -43,16 +87,18 @@ class CharTokenizer:
     def token_id(self, ch):
         return FIRST_FREE_ID + zlib.crc32(ch.encode("utf-8")) % (self.vocab_size - FIRST_FREE_ID)
 
+    def body(self, text):
+        return [self.token_id(c) for c in text if not c.isspace()]
+
     def encode(self, text):
-        body = [self.token_id(c) for c in text if not c.isspace()]
-        body = body[: self.max_length - 2]
+        body = self.body(text)[: self.max_length - 2]
         return [CLS] + body + [SEP]
 
     def __call__(self, texts, pad_to=None):
         return _pack([self.encode(t) for t in texts], self.max_length, pad_to)
 
 
-class WordPieceTokenizer:
+class WordPieceTokenizer(_PairMixin):
     """BERT WordPiece over a local vocab file, as the published tokenizer computes it
     (`tokenizers` BertNormalizer + BertPreTokenizer + WordPiece, i.e.
     transformers.BertTokenizer; pinned by tests/golden/wordpiece_golden.json):
@@ -144,11 +190,14 @@ class WordPieceTokenizer:
             start = end
         return out
 
-    def encode(self, text):
+    def body(self, text):
         body = []
         for w in self._basic(text):
             body.extend(self._wordpiece(w))
-        return [self.cls] + body[: self.max_length - 2] + [self.sep]
+        return body
+
+    def encode(self, text):
+        return [self.cls] + self.body(text)[: self.max_length - 2] + [self.sep]
 
     def __call__(self, texts, pad_to=None):
         return _pack([self.encode(t) for t in texts], self.max_length, pad_to)
@@ -221,3 +270,21 @@ class NativeTokenizer:
     def encode(self, text):
         ids, mask = self([text])
         return ids[0, :int(mask[0].sum())].tolist()
+
+    def pairs(self, firsts, seconds, pad_to=None):
+        """(first, second) text pairs as [CLS] A [SEP] B [SEP] -> (ids, types, mask) int32
+        [n, L] (mq_tokenizer_encode_pairs; truncation longest-first to max_length >= 5)."""
+        import ctypes
+        from . import _lib
+        firsts, seconds = list(firsts), list(seconds)
+        if len(firsts) != len(seconds):
+            raise ValueError("pairs: %d first texts, %d second texts" % (len(firsts), len(seconds)))
+        n = len(firsts)
+        cap = max(self.max_length, pad_to or 0)
+        bufs = [np.zeros(max(1, n * cap), dtype=np.int32) for _ in range(3)]
+        a = (ctypes.c_char_p * max(1, n))(*[t.encode("utf-8") for t in firsts])
+        b = (ctypes.c_char_p * max(1, n))(*[t.encode("utf-8") for t in seconds])
+        L = ctypes.c_int()
+        _lib.call("mq_tokenizer_encode_pairs", self._h, a, b, n, int(pad_to or 0), _lib.ptr(bufs[0]),
+                  _lib.ptr(bufs[1]), _lib.ptr(bufs[2]), ctypes.byref(L))
+        return tuple(x[:n * L.value].reshape(n, L.value).copy() for x in bufs)

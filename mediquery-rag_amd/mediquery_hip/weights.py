@@ -109,3 +109,46 @@ def load_safetensors(path, cfg: BertConfig):
     for k, v in raw.items():
         sd[k[5:] if k.startswith("bert.") else k] = v
     return sd
+
+
+# ---- cross-encoder head (BertForSequenceClassification: BertPooler + classifier) ----------
+# A separate upload (mq_encoder_load_head): the blob above and hf_names do not include it.
+HEAD_NAMES = ("pooler.dense.weight", "pooler.dense.bias", "classifier.weight", "classifier.bias")
+
+
+def head_shapes(cfg: BertConfig, n_labels=1):
+    H = cfg.hidden
+    return ((H, H), (H,), (n_labels, H), (n_labels,))
+
+
+def synthetic_head_state_dict(cfg: BertConfig, seed: int = 0, n_labels: int = 1):
+    """Seeded head: N(0, 0.02) for the four tensors of HEAD_NAMES, generator i of
+    default_rng([seed, 10000 + i]) (apart from every stream synthetic_state_dict uses)."""
+    sd = {}
+    for i, (name, shape) in enumerate(zip(HEAD_NAMES, head_shapes(cfg, n_labels))):
+        rng = np.random.default_rng([seed, 10000 + i])
+        sd[name] = (0.02 * rng.standard_normal(shape, dtype=np.float32)).astype(np.float32, copy=False)
+    return sd
+
+
+def head_from_state_dict(sd, cfg: BertConfig = None):
+    """The four head tensors of a loaded state dict (load_safetensors strips "bert.", so a
+    BertForSequenceClassification checkpoint carries exactly HEAD_NAMES) as contiguous fp32
+    arrays -> (pooler_w [H, H], pooler_b [H], cls_w [n_labels, H], cls_b [n_labels]).
+    KeyError names the missing tensors; ValueError a shape that does not fit."""
+    missing = [n for n in HEAD_NAMES if n not in sd]
+    if missing:
+        raise KeyError("no cross-encoder head in these weights: missing %s (a "
+                       "BertForSequenceClassification checkpoint carries %s)"
+                       % (", ".join(missing), ", ".join(HEAD_NAMES)))
+    out = []
+    for n in HEAD_NAMES:
+        v = sd[n]
+        v = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        out.append(np.ascontiguousarray(v, dtype=np.float32))
+    pw, pb, cw, cb = out
+    H = pw.shape[0] if cfg is None else cfg.hidden
+    if pw.shape != (H, H) or pb.shape != (H,) or cw.ndim != 2 or cw.shape[1] != H or cb.shape != (cw.shape[0],):
+        raise ValueError("cross-encoder head shapes %s do not fit hidden %d"
+                         % ([tuple(a.shape) for a in out], H))
+    return pw, pb, cw, cb
