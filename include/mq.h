@@ -386,6 +386,18 @@ int mq_encoder_set_graphs(mq_encoder* enc, int enabled);
  *                                projection of every token and the attention kernel.  The same
  *                                sums re-associated: results agree to fp32 rounding.  Mean pooling
  *                                and L = 1 run as with 0, bit for bit.
+ *   MQ_ENC_OPT_QKV_ATTN          split-f32 precision, x6_presplit 1, batched forward, L == 32, hidden
+ *                                == 64 * heads and a multiple of 192, the QKV GEMM one that fills
+ *                                the chip on the 128 x 192 split-f32 tile: 1 (default) = the QKV
+ *                                launch of every full-M layer but a CLS-only last one ends in the
+ *                                attention itself - one head per tile, Q | K | V kept in the
+ *                                accumulators, ctx written straight from them; no qkv buffer
+ *                                traffic and no attention launch on those layers; 0 = the QKV
+ *                                launch and the attention launch.  Q, K, V are the same bits; the
+ *                                softmax sums are associated differently: results agree to fp32
+ *                                rounding.  With x6_presplit 0 the same attention follows the QKV
+ *                                launch as a launch of its own: the same bits as x6_presplit 1.
+ *                                Every other shape runs as with 0, bit for bit.
  * Setting an option drops the handle's captured graphs. */
 #define MQ_ENC_OPT_ROWS_MAX 0
 #define MQ_ENC_OPT_ROWS_SPLITS 1
@@ -400,6 +412,7 @@ int mq_encoder_set_graphs(mq_encoder* enc, int enabled);
 #define MQ_ENC_OPT_ROWS_PLANES 10
 #define MQ_ENC_OPT_LN_FOLD 11
 #define MQ_ENC_OPT_CLS_KFREE 12
+#define MQ_ENC_OPT_QKV_ATTN 13
 int mq_encoder_set_option(mq_encoder* enc, int option, int value);
 int mq_encoder_get_option(const mq_encoder* enc, int option, int* value);
 int mq_encoder_set_timing(mq_encoder* enc, int enabled);
@@ -503,7 +516,7 @@ int mq_debug_gemm_x6p(const float* A, const void* W3, const float* bias, const f
  * stats_in [M][8] (mean, M2) pairs and g / b [N] (stats_in NULL: the residual as it is), and
  * the partials of out written to stats_out [M][8]; N = 768.  epi 6 / 7 / 8 = the consumers
  * (bias / GELU erf / GELU tanh): out = epi(rho_r (acc - mu_r s_fold[n]) + bias[n]), (mu, rho)
- * from stats_in and eps; K = 768.  mq_debug_ln_fold_weight builds Wg = g W (whose W3 image the
+ * from stats_in and eps (the encoder's run at K = 768).  mq_debug_ln_fold_weight builds Wg = g W (whose W3 image the
  * consumer multiplies), s and c (the consumer's bias) from W [N][K], bias, g, b. */
 int mq_debug_gemm_x6p_ln(const float* A, const void* W3, const float* bias, const float* resid,
                          float* out, int M, int N, int K, int epi, int tile, const float* stats_in,
@@ -511,6 +524,16 @@ int mq_debug_gemm_x6p_ln(const float* A, const void* W3, const float* bias, cons
                          float eps, void* stream);
 int mq_debug_ln_fold_weight(const float* W, const float* bias, const float* g, const float* b, int N,
                             int K, float* Wg, float* s_out, float* c_out, void* stream);
+/* One K2p QKV launch whose epilogue is the L = 32 attention (MQ_ENC_OPT_QKV_ATTN; the 128 x 192
+ * tile): ctx [M][64 heads] = attention of qkv = A W^T + bias (epi 9) or rho_r (A W^T - mu_r
+ * s_fold[n]) + bias[n] (epi 10, (mu, rho) from stats_in [M][8] and eps) over sequences of 32
+ * rows, W3 the image of W [3 * 64 heads][K], mask [M] int32, Q scaled by `scale`.  No qkv is
+ * written.  M % 32 == 0, K % 32 == 0.  max_workgroups 0 = one workgroup per CU, else a multiple
+ * of 8: at most that many, each walking more tiles.  Asynchronous on `stream`. */
+int mq_debug_gemm_x6p_attn(const float* A, const void* W3, const float* bias, const int* mask,
+                           float* ctx, int M, int K, int heads, float scale, int epi,
+                           const float* stats_in, const float* s_fold, float eps, int max_workgroups,
+                           void* stream);
 /* One attention launch (K3) on device buffers: ctx [B*L][H] = softmax(scale Q K^T over the
  * keys with mask != 0) V per (sequence, head); a query whose keys are all masked gives 0.
  * qkv is [B*L][3H] row-major, Q | K | V columns, head h at column h * 64 of each third

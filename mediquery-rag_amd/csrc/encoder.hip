@@ -2252,6 +2252,11 @@ constexpr bool kLnFoldDefault = MQ_LN_FOLD_DEFAULT != 0;
 #define MQ_CLS_KFREE_DEFAULT 1
 #endif
 constexpr bool kClsKfreeDefault = MQ_CLS_KFREE_DEFAULT != 0;
+// MQ_ENC_OPT_QKV_ATTN's default (DESIGN.md section 4 has the A/B that decides it)
+#ifndef MQ_QKV_ATTN_DEFAULT
+#define MQ_QKV_ATTN_DEFAULT 1
+#endif
+constexpr bool kQkvAttnDefault = MQ_QKV_ATTN_DEFAULT != 0;
 
 // Stage labels for the optional per-kernel-class event timeline.
 enum Stage { ST_EMBED = 0, ST_QKV, ST_ATTN, ST_OPROJ, ST_LN, ST_FFN_UP, ST_FFN_DOWN, ST_POOL, ST_N };
@@ -2305,6 +2310,7 @@ struct mq_encoder {
   Buf wfold3, wfoldf, sfold;    // its gamma-scaled weights (W3 images / fp32) and s, c vectors
   bool rows_planes = false;     // few-row forward: keep the two-plane hand-offs (no FL_ACC merge)
   bool cls_kfree = kClsKfreeDefault;  // CLS pooling, batched forward: the last layer without K / V
+  bool qkv_attn = kQkvAttnDefault;    // split-f32 batched forward, L = 32: attention in the QKV epilogue
   Buf wkt;                      // its Wk^T of the last layer [H][H], built at weight load
   Buf cls;                      // its [B] rows: normalised CLS rows, q (H each), u, z (heads H each), live
   // cross-encoder head (mq_encoder_load_head): Wp [H][H], bp [H], Wc [n_labels][H], bc [n_labels]
@@ -2617,6 +2623,17 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* types, const int* mask
   float* fst2 = e->lnst.p + (size_t)2 * M * nt;
   bool raw = false;  // fold: x holds the previous layer's raw FFN-down sum (+ fst2), not LN2 of it
   bool pooled = false;  // CLS_KFREE: the last FFN-down's reduction has written the embeddings
+  // MQ_ENC_OPT_QKV_ATTN: L = 32, 64-wide heads, whole 192-column tiles per head, and the QKV
+  // GEMM one that launch_gemm runs on K2p's 128 x 192 tile (no split-K: M > 256; the split-f32
+  // tiles fill the chip; x6p_pick_tile takes tile 0); the full-M QKV of every layer but a
+  // CLS-only last one takes it, LN2 of the previous layer folded in or not as `fold` says.
+  // On the re-split tiles (x6_presplit 0) the QKV GEMM runs as it did and the epilogue's
+  // attention follows as a launch of its own (launch_attn32): x6_presplit 0 / 1 give the same bits.
+  const bool attn_shape = e->qkv_attn && e->precision == MQ_DTYPE_F32X6 && L == 32 && H == 64 * c.heads &&
+                          H % 192 == 0 && H % 32 == 0 && M > 256 && !lnl &&
+                          (int64_t)((M + 127) / 128) * ((3 * H + 191) / 192) >= e->num_cus &&
+                          x6p_pick_tile(M, 3 * H, e->num_cus) == 0 && (int64_t)M * H < (1ll << 29);
+  const bool qkv_attn = attn_shape && e->x6_presplit;
   auto fold_gemm = [&](auto epi, GemmArgs g, int stage) {
     e->tl.mark(s, stage);
     if (!e->x6_presplit) g.W3 = nullptr;
@@ -2659,6 +2676,8 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* types, const int* mask
     const int lnt = M <= 256 && (int)li >= e->resident_layers ? 1 : 0;
     // the CLS-only tail (the B CLS rows past attention) runs unfolded
     const bool fold_layer = fold && !(cls_only && L > 1);
+    bool attn_done = false;   // qkv_attn: this layer's QKV launch has written ctx
+    bool attn_after = false;  // ... or the same attention follows the plain QKV launch
     // the folded QKV weights' rows [row0, ..): LN2 of the previous layer applied in the epilogue
     auto qkv_fold = [&](GemmArgs g, int row0) {
       g.W = w.wqkvgf ? w.wqkvgf + (int64_t)row0 * H : nullptr;
@@ -2717,18 +2736,36 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* types, const int* mask
       GemmArgs q{e->slab.p, e->slab.n, e->x.p, L * H, w.wqkv, w.bqkv, nullptr, 0, e->qkv.p, L * 3 * H, B, H, H, lnt};
       q.W3 = w.wqkv3;
       gemm<EPI_BIAS>(e, q, ST_QKV, s);
+    } else if (qkv_attn && (raw ? w.wqkvg3 != nullptr : w.wqkv3 != nullptr)) {
+      // L = 32 attention in the QKV GEMM's epilogue (EPI_ATTN_*): ctx straight from the
+      // accumulators, no qkv written and no attention launch; folded or not as the plain QKV is
+      X6pArgs a{qkv_in, H, raw ? w.wqkvg3 : w.wqkv3, raw ? w.wqkvc : w.bqkv, nullptr, 0, e->ctx.p, H, M, 3 * H, H};
+      if (raw) {
+        a.lf.s = w.wqkvs;
+        a.lf.stats_in = fst2;
+        a.lf.eps = c.ln_eps;
+      }
+      a.at.mask = mask;
+      a.at.scale = scale;
+      e->tl.mark(s, ST_QKV);
+      launch_gemm_x6p(a, raw ? EPI_ATTN_LNFOLD : EPI_ATTN_BIAS, 0, e->num_cus, s);
+      attn_done = true;
     } else {
       GemmArgs qkv{e->slab.p, e->slab.n, qkv_in, H, w.wqkv, w.bqkv, nullptr, 0, e->qkv.p, 3 * H, M, 3 * H, H};
       qkv.W3 = w.wqkv3;
       qkv_gemm(qkv);
+      attn_after = attn_shape;
     }
     y_pending = false;
     const bool resid_raw = raw && fold_layer;  // (the tail's residual rows were normalised above)
     raw = false;
-    if (!kfree) {
+    if (!kfree && !attn_done) {
       e->tl.mark(s, ST_ATTN);
       const int qt = cls_only ? 1 : q_tiles;
-      launch_attention(B, L, c.heads, qt, H, scale, e->qkv.p, mask, e->ctx.p, s);
+      if (attn_after)
+        launch_attn32(e->qkv.p, mask, e->ctx.p, M, H, scale, s);
+      else
+        launch_attention(B, L, c.heads, qt, H, scale, e->qkv.p, mask, e->ctx.p, s);
     }
     const bool lnl_layer = lnl && !cls_only;
     // x = LN1(x + ctx Wo^T + bo)  (compact [rows, H], through y) - or, deferred, y + partials
@@ -3505,6 +3542,10 @@ int mq_encoder_set_option(mq_encoder* e, int option, int value) {
       MQ_CHECK_ARG(value == 0 || value == 1, "cls_kfree must be 0 or 1 (got %d)", value);
       e->cls_kfree = value != 0;
       break;
+    case MQ_ENC_OPT_QKV_ATTN:
+      MQ_CHECK_ARG(value == 0 || value == 1, "qkv_attn must be 0 or 1 (got %d)", value);
+      e->qkv_attn = value != 0;
+      break;
     default:
       MQ_FAIL(MQ_EINVAL, "unknown encoder option %d", option);
   }
@@ -3531,6 +3572,7 @@ int mq_encoder_get_option(const mq_encoder* e, int option, int* value) {
     case MQ_ENC_OPT_ROWS_PLANES: *value = e->rows_planes ? 1 : 0; break;
     case MQ_ENC_OPT_LN_FOLD: *value = e->ln_fold ? 1 : 0; break;
     case MQ_ENC_OPT_CLS_KFREE: *value = e->cls_kfree ? 1 : 0; break;
+    case MQ_ENC_OPT_QKV_ATTN: *value = e->qkv_attn ? 1 : 0; break;
     default: MQ_FAIL(MQ_EINVAL, "unknown encoder option %d", option);
   }
   return MQ_OK;

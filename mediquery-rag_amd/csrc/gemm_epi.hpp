@@ -23,9 +23,14 @@ enum Epi {
   EPI_RESID_LN_STATS = 5,
   EPI_BIAS_LNFOLD = 6,
   EPI_GELU_ERF_LNFOLD = 7,
-  EPI_GELU_TANH_LNFOLD = 8
+  EPI_GELU_TANH_LNFOLD = 8,
+  // L = 32 attention in the QKV epilogue (K2p's 128 x 192 loader-wave tile only, attn_wave_tile
+  // below): EPI_BIAS / EPI_BIAS_LNFOLD whose Q, K, V never leave the registers; out is ctx [M, H]
+  EPI_ATTN_BIAS = 9,
+  EPI_ATTN_LNFOLD = 10
 };
 constexpr bool epi_is_lnfold(int epi) { return epi >= EPI_BIAS_LNFOLD && epi <= EPI_GELU_TANH_LNFOLD; }
+constexpr bool epi_is_attn(int epi) { return epi == EPI_ATTN_BIAS || epi == EPI_ATTN_LNFOLD; }
 
 // GELU, branch-free (it runs 64 times per lane in every FFN-up tile epilogue; ocml's erff
 // is ~50 VALU + a divergent branch per element and measured as the FFN-up epilogue's cost).
@@ -455,6 +460,174 @@ __device__ __forceinline__ void store_wave_tile16(floatx4 (&acc)[MB][NB], int wr
         if constexpr (EPI == EPI_RESID) v += resid[(int64_t)row * ldr + col];
         out[(int64_t)row * ldo + col] = v;
       }
+  }
+}
+
+// L = 32 attention as the epilogue of the QKV GEMM (EPI_ATTN_BIAS / EPI_ATTN_LNFOLD; K2p's
+// 128 x 192 tile with its W3 column blocks gathered per head, gemm_x6p.hip).  The wave (wm, wn)
+// holds, for head `head` and the 64 rows from wr0 - two whole sequences - the 16-column blocks
+// n = 0, 1: Q, 2, 3: K, 4, 5: V of head dims 32 wn .. + 31.  Per sequence:
+//   1  Q, K, V are finished in the registers exactly as EPI_BIAS / EPI_BIAS_LNFOLD store them,
+//      Q times `scale`;
+//   2  the Q and K halves (32 x 32) go through the wave's private staging `stg` ([64][kAttnSt]
+//      floats, Q rows then K rows) and come back rows-on-lanes: lane (c, g) reads dims 4 g + i
+//      and 16 + 4 g + i of row c, step i of the 8-step v_mfma_f32_16x16x4_f32 chain taking
+//      k-slot g <-> dim 4 g + i (16 (i >> 2) + 4 g + (i & 3)), the same for Q and K: the partial
+//      S^T[key][query] over the wave's 32 head dims, four 16 x 16 blocks;
+//   3  both sequences' partials overwrite the staging (the wave's own reads have returned: one
+//      wave's LDS operations execute in order), ONE workgroup barrier - which the loader waves
+//      execute too - and the partner's (same wm, other wn) partials are added: a + b is
+//      commutative, so both waves hold the same bits;
+//   4  softmax over keys in registers: the 8 keys 16 kb + 4 g + e of a lane, then the lane
+//      groups g by two xor shuffles; masked keys weigh exactly 0, no live key gives l = 0 and
+//      ctx exactly 0; expf and o (1 / l) as attention_kernel;
+//   5  O[q][d] = sum P V: register e of the S^T block (kb, qb) is operand A (query c, key 16 kb +
+//      4 g + e) and register e of V's accumulator block is operand B (the same key, dim c): no
+//      data movement.  Rows >= M are not stored.
+// Every wave executes the barrier exactly once, whatever M.
+// PRE (attn32_kernel, gemm_x6p.hip: the same attention as a launch of its own): acc already
+// holds the finished Q, K, V as an unfused QKV launch stored them; only Q's scale is applied.
+// Everything after step 1 is this one function: the same bits as the epilogue.
+constexpr int kAttnSt = 36;                     // staging row stride in floats (32 + 4)
+constexpr int kAttnStage = 64 * kAttnSt * 4;    // bytes of staging per wave (>= the 8 KB of partials)
+template <bool FOLD, bool PRE = false>
+__device__ __forceinline__ void attn_wave_tile(floatx4 (&acc)[4][6], int wr0, int head, int wn, int M, int H,
+                                               const float* __restrict__ bias, const LnFold& lf,
+                                               const int* __restrict__ mask, float scale,
+                                               float* __restrict__ ctx, int lane, unsigned char* stg,
+                                               const unsigned char* partner) {
+  static_assert(kAttnStage >= 8 * 1024, "the partials of two sequences fit the staging");
+  const int c = lane & 15, g = lane >> 4;
+  // key-live bits: bit 32 s + k = key k of sequence s (rows past M: clamped, never stored)
+  const unsigned long long kbits = __ballot(mask[min(wr0 + lane, M - 1)] != 0);
+  float own_mu = 0.f, own_rho = 0.f;
+  if constexpr (FOLD) ln_row_own<4>(lf.stats_in, wr0, M, lf.eps, lane, own_mu, own_rho);
+  if constexpr (PRE) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+      for (int n = 0; n < 2; ++n)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[m][n][e] = acc[m][n][e] * scale;
+  } else {
+    float bv[6], sv[6];
+#pragma unroll
+    for (int n = 0; n < 6; ++n) {
+      const int col = (n >> 1) * H + 64 * head + 32 * wn + 16 * (n & 1) + c;
+      bv[n] = bias[col];
+      if constexpr (FOLD) sv[n] = lf.s[col];
+    }
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float mu = 0.f, rho = 0.f;
+        if constexpr (FOLD) {
+          mu = ln_row_bcast(own_mu, lane, m, e);
+          rho = ln_row_bcast(own_rho, lane, m, e);
+        }
+#pragma unroll
+        for (int n = 0; n < 6; ++n) {
+          float v;
+          if constexpr (FOLD)
+            v = __fmaf_rn(rho, __fmaf_rn(-mu, sv[n], acc[m][n][e]), bv[n]);
+          else
+            v = acc[m][n][e] + bv[n];
+          acc[m][n][e] = n < 2 ? v * scale : v;
+        }
+      }
+  }
+  float* sf = reinterpret_cast<float*>(stg);
+  floatx4 sp[2][2][2];  // [sequence][key block][query block]
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)  // Q rows 0-31, K rows 32-63
+#pragma unroll
+      for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+        for (int nd = 0; nd < 2; ++nd)
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            sf[(32 * t + 16 * mb + 4 * g + e) * kAttnSt + 16 * nd + c] = acc[2 * s + mb][2 * t + nd][e];
+    floatx4 qf[2][2], kf[2][2];
+#pragma unroll
+    for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        qf[blk][hf] = *reinterpret_cast<const floatx4*>(&sf[(16 * blk + c) * kAttnSt + 16 * hf + 4 * g]);
+        kf[blk][hf] = *reinterpret_cast<const floatx4*>(&sf[(32 + 16 * blk + c) * kAttnSt + 16 * hf + 4 * g]);
+      }
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+      for (int qb = 0; qb < 2; ++qb) {
+        floatx4 st = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          st = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[kb][i >> 2][i & 3], qf[qb][i >> 2][i & 3], st, 0, 0, 0);
+        sp[s][kb][qb] = st;
+      }
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+    *reinterpret_cast<floatx4*>(stg + i * 1024 + lane * 16) = sp[i >> 2][(i >> 1) & 1][i & 1];
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // the exchange barrier
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+    sp[i >> 2][(i >> 1) & 1][i & 1] += *reinterpret_cast<const floatx4*>(partner + i * 1024 + lane * 16);
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const unsigned kb32 = (unsigned)(kbits >> (32 * s));
+    float inv[2];
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+      float mx = -INFINITY;
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const bool live = (kb32 >> (16 * kb + 4 * g + e)) & 1u;
+          sp[s][kb][qb][e] = live ? sp[s][kb][qb][e] : -INFINITY;
+          mx = fmaxf(mx, sp[s][kb][qb][e]);
+        }
+      mx = fmaxf(mx, __shfl_xor(mx, 16));
+      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      float l = 0.f;
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float v = sp[s][kb][qb][e];
+          const float p = v == -INFINITY ? 0.f : expf(v - mx);
+          sp[s][kb][qb][e] = p;
+          l += p;
+        }
+      l += __shfl_xor(l, 16);
+      l += __shfl_xor(l, 32);
+      inv[qb] = l > 0.f ? 1.0f / l : 0.f;  // of query 16 qb + c, in every lane group
+    }
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+      floatx4 o[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+          for (int nd = 0; nd < 2; ++nd)
+            o[nd] = __builtin_amdgcn_mfma_f32_16x16x4f32(sp[s][kb][qb][e], acc[2 * s + kb][4 + nd][e], o[nd], 0, 0, 0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float iq = __shfl(inv[qb], 4 * g + e);  // of query 16 qb + 4 g + e
+        const int row = wr0 + 32 * s + 16 * qb + 4 * g + e;
+        if (row < M) {
+          float* dst = ctx + (int64_t)row * H + 64 * head + 32 * wn + c;
+          dst[0] = o[0][e] * iq;
+          dst[16] = o[1][e] * iq;
+        }
+      }
+    }
   }
 }
 

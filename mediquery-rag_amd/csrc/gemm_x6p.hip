@@ -192,10 +192,35 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
                                                              const float* __restrict__ bias,
                                                              const float* __restrict__ resid, int ldr,
                                                              float* __restrict__ out, int ldo, int M, int N,
-                                                             int K, int rx, LnFold lf) {
+                                                             int K, int rx, LnFold lf, AttnEpi at) {
   __shared__ __attribute__((aligned(1024))) unsigned char lds[T::NBUF * T::STAGE];
   const unsigned lds0 = (unsigned)(uintptr_t)(x6p_lds_t*)lds;
   constexpr bool HAND = EPI == EPI_RESID_LN_STATS && T::LDR && T::M16 && !T::DEEP && T::NBUF == 3 && !FORMER;
+  // ATTN (EPI_ATTN_BIAS / EPI_ATTN_LNFOLD, X6p0 only): the tile's W3 column blocks are gathered
+  // per head - tile column index = head, blocks [Q d0-31 | K d0-31 | V d0-31 | Q d32-63 | K d32-63
+  // | V d32-63], so compute wave wn holds Q | K | V of head dims 32 wn .. + 31 for two whole
+  // 32-row sequences - and the epilogue is the attention itself (gemm_epi.hpp attn_wave_tile),
+  // worked in the ring slot that is free at every tile end:
+  //   stage j, a tile's last, sits in slot j % 3.  The compute waves read it in iteration j - 1
+  //   and wait lgkmcnt(0) before B(j + 1), so past B(j + 1) no wave has a read of it in flight.
+  //   The loader refills slot j % 3 (stage j + 3) only after B(j + 2), which the compute waves
+  //   reach after their epilogue.  The four waves' staging (4 x kAttnStage <= STAGE) lives there.
+  //   Slot (j + 1) % 3 holds stage j + 1 until B(j + 3): after the epilogue the compute waves
+  //   read and split its operands again, as the prologue does, so the copies prefetched in
+  //   iteration j are dead across the epilogue.
+  //   Barriers, per role (every wave of the workgroup executes each exactly once):
+  //                         compute waves                        loader waves
+  //     prologue  B(0)      before reading stage 0               after vmcnt: stage 0 landed
+  //     stage j   B(j + 1)  top of iteration j (tile's last      stage j + 1 landed
+  //                         stage: after lgkmcnt(0))
+  //     tile end  X(j)      in the epilogue, partials written    after issuing stage j + 2,
+  //               (j % nst == nst - 1)        and lgkmcnt(0)     waiting on nothing
+  //   i.e. S + 1 + n_tiles on both sides, ragged tiles included: nothing about a barrier
+  //   depends on M.
+  constexpr bool ATTN = epi_is_attn(EPI);
+  static_assert(!ATTN || (T::LDR && T::M16 && !T::DEEP && T::NBUF == 3 && T::WAVES_M == 2 && T::WAVES_N == 2 &&
+                          T::TM == 2 && T::TN == 3 && 4 * kAttnStage <= T::STAGE),
+                "attention epilogue: the 128 x 192 loader-wave tile");
   static_assert(!HAND || (T::NW == 4 && 2 * T::WM * T::WN * 4 <= T::STAGE && T::WN == kLnPartW && T::STAGE % 1024 == 0),
                 "hand-off: two wave tiles of t per ring slot");
   const int lane = threadIdx.x & 63;
@@ -265,7 +290,8 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
     } else {
       if constexpr (T::DBG & 32) return;
       const int b = in - T::NA, nbl = b / 3, p = b - nbl * 3;
-      const int nbg = min((is_n0 >> 5) + nbl, nbw - 1);
+      int nbg = min((is_n0 >> 5) + nbl, nbw - 1);
+      if constexpr (ATTN) nbg = (nbl % 3) * (N / 96) + 2 * (is_n0 / T::BN) + nbl / 3;  // (H / 32 blocks per third)
       const unsigned char* wbase = W3 + ((size_t)(nbg * nk + kt) * 3 + p) * 1024;
       x6p_glds(wbase, (unsigned)lane * 16u, dst + T::KS * T::A_SUB + ks * T::B_SUB + b * 1024);
     }
@@ -487,9 +513,16 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
         asm volatile("s_barrier" ::: "memory");  // B(S + 1): the hand-off
         return;
       }
+      int l_st = 0;
       for (int j = 0; j < S; ++j) {
         wait_stages(IC<T::AHEAD - 2>{});  // stage j + 1 landed
         issue((j + T::AHEAD) % T::NBUF);  // stage j + AHEAD
+        if constexpr (ATTN) {
+          if (++l_st == nst) {  // X(j): the compute waves' exchange barrier of this tile end
+            l_st = 0;
+            asm volatile("s_barrier" ::: "memory");
+          }
+        }
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing re-read DMAs
       return;
@@ -556,19 +589,23 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
     };
     zero4();
     wait_stages(IC<T::AHEAD - 1>{});  // stage 0 landed
+    // the operands of a stage whole: A blocks read and split (the last left in `raw`), B read
+    auto load_ops = [&](const unsigned char* st) __attribute__((always_inline)) {
 #pragma unroll
-    for (int m = 0; m < MB; ++m) {
-      rd_raw(lds, m, 0);
-      rd_raw(lds, m, 1);
-      if (m < MB - 1) {
+      for (int m = 0; m < MB; ++m) {
+        rd_raw(st, m, 0);
+        rd_raw(st, m, 1);
+        if (m < MB - 1) {
 #pragma unroll
-        for (int q = 0; q < NSUB; ++q) sub(m, q);
+          for (int q = 0; q < NSUB; ++q) sub(m, q);
+        }
       }
-    }
 #pragma unroll
-    for (int n = 0; n < NB16; ++n)
+      for (int n = 0; n < NB16; ++n)
 #pragma unroll
-      for (int p = 0; p < 3; ++p) rd_b(lds, n, p);
+        for (int p = 0; p < 3; ++p) rd_b(st, n, p);
+    };
+    load_ops(lds);
     int rb = 1 % T::NBUF;          // ring slot of stage j + 1
     int ib = T::AHEAD % T::NBUF;   // ring slot stage j + AHEAD goes to (8-wave tiles)
     for (int j = 0; j < S; ++j) {
@@ -579,6 +616,9 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
         wait_stages(IC<T::AHEAD - 2>{});
       } else {
         if constexpr (T::DEEP) __builtin_amdgcn_s_waitcnt(0xC07F);
+        if constexpr (ATTN) {  // a tile's last stage: its slot is the epilogue's, no read of it may be in flight
+          if (c_st == nst - 1) __builtin_amdgcn_s_waitcnt(0xC07F);
+        }
         asm volatile("s_barrier" ::: "memory");
       }
       // (HAND, last iteration: slot rb = S % 3 holds no stage - the loader waves are writing t
@@ -614,8 +654,18 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
         c_st = 0;
         int m0, n0;
         coords(c_i, m0, n0);
-        store_wave_tile16<EPI, MB, NB16>(acc4, m0 + wm * T::WM, n0 + wn * T::WN, M, N, bias, resid, ldr, out, ldo,
-                                         lane, lf);
+        if constexpr (ATTN) {
+          unsigned char* fs = lds + (j % T::NBUF) * T::STAGE;  // stage j's slot: free until B(j + 2)
+          attn_wave_tile<EPI == EPI_ATTN_LNFOLD>(acc4, m0 + wm * T::WM, n0 / T::BN, wn, M, N / 3, bias, lf, at.mask,
+                                                 at.scale, out, lane, fs + cw * kAttnStage,
+                                                 fs + (cw ^ 1) * kAttnStage);
+          // stage j + 1 again: its prefetched copies died above.  Unconditional, so that no path
+          // carries them across the epilogue (after the last tile the values are never used)
+          load_ops(st);
+        } else {
+          store_wave_tile16<EPI, MB, NB16>(acc4, m0 + wm * T::WM, n0 + wn * T::WN, M, N, bias, resid, ldr, out, ldo,
+                                           lane, lf);
+        }
         zero4();
         ++c_i;
       }
@@ -702,6 +752,30 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing re-read DMAs
 }
 
+// EPI_ATTN_*'s attention from a stored qkv (launch_attn32): one workgroup of 4 waves per (128
+// rows, head), wave (wm, wn) loading the accumulator image the fused kernel's compute wave (wm,
+// wn) holds at its tile end - block (m, n), register e of lane (c, g) = row 16 m + 4 g + e, column
+// 16 (n & 1) + c of Q | K | V (n >> 1) for head dims 32 wn .. + 31 - rows past M clamped, as the
+// fused kernel's A loads are.
+__global__ __launch_bounds__(256) void attn32_kernel(const float* __restrict__ qkv, const int* __restrict__ mask,
+                                                     float* __restrict__ ctx, int M, int H, float scale) {
+  __shared__ __attribute__((aligned(16))) unsigned char stg[4 * kAttnStage];
+  const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+  const int cw = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), wm = cw >> 1, wn = cw & 1;
+  const int heads = H / 64, head = blockIdx.x % heads, wr0 = (blockIdx.x / heads) * 128 + 64 * wm;
+  floatx4 acc[4][6];
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float* row = qkv + (int64_t)min(wr0 + 16 * m + 4 * g + e, M - 1) * (3 * H) + 64 * head + 32 * wn + c;
+#pragma unroll
+      for (int n = 0; n < 6; ++n) acc[m][n][e] = row[(n >> 1) * H + 16 * (n & 1)];
+    }
+  attn_wave_tile<false, true>(acc, wr0, head, wn, M, H, nullptr, LnFold{}, mask, scale, ctx, lane,
+                              stg + cw * kAttnStage, stg + (cw ^ 1) * kAttnStage);
+}
+
 // W [N][K] fp32 -> W3: one thread per (row n < Np, 8-wide k chunk); rows past N are zero.
 __global__ __launch_bounds__(256) void split_w3_kernel(const float* __restrict__ W, int N, int K,
                                                        uintx4* __restrict__ w3) {
@@ -760,14 +834,15 @@ void launch_t(const X6pArgs& g, int num_cus, hipStream_t s) {
     }
   }
   const int tiles = ((g.M + T::BM - 1) / T::BM) * ((g.N + T::BN - 1) / T::BN);
-  const int grid = (std::min(tiles, num_cus) + 7) / 8 * 8;  // one workgroup per CU, a multiple of 8
+  int grid = (std::min(tiles, num_cus) + 7) / 8 * 8;  // one workgroup per CU, a multiple of 8
+  if (g.max_wg > 0) grid = std::min(grid, g.max_wg);
   const int tiles_m = (g.M + T::BM - 1) / T::BM, tiles_n = (g.N + T::BN - 1) / T::BN;
   int rx = g.rx;
   if (rx < 0) rx = region_pick_rx(tiles_m, tiles_n, (double)T::BM * g.K * 4, (double)T::BN * g.K * 6, grid);
   if (rx > 0 && (8 % rx != 0 || rx > tiles_n || 8 / rx > tiles_m || grid < 8)) rx = 0;  // (a region per XCD)
   hipLaunchKernelGGL((gemm_x6p_kernel<T, EPI, FORMER>), dim3(grid), dim3(T::THREADS), 0, s, g.A, g.lda,
                      static_cast<const unsigned char*>(g.W3), g.bias, g.resid, g.ldr, g.out, g.ldo, g.M, g.N, g.K, rx,
-                     g.lf);
+                     g.lf, g.at);
 }
 
 template <int EPI>
@@ -850,6 +925,11 @@ void launch_ln_fold_weight(const float* W, const float* bias, const float* g, co
                      s_out, c_out);
 }
 
+void launch_attn32(const float* qkv, const int* mask, float* ctx, int M, int H, float scale, hipStream_t s) {
+  hipLaunchKernelGGL(attn32_kernel, dim3((unsigned)(((M + 127) / 128) * (H / 64))), dim3(256), 0, s, qkv, mask, ctx, M,
+                     H, scale);
+}
+
 void launch_split_w3(const float* W, int N, int K, void* w3, hipStream_t s) {
   const int64_t n = (int64_t)((N + 31) & ~31) * (K >> 3);
   hipLaunchKernelGGL(split_w3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W, N, K,
@@ -882,6 +962,8 @@ void launch_gemm_x6p(const X6pArgs& g, int epi, int tile, int num_cus, hipStream
     case EPI_BIAS_LNFOLD: launch_tile_fold<EPI_BIAS_LNFOLD>(g, tile, num_cus, s); return;
     case EPI_GELU_ERF_LNFOLD: launch_tile_fold<EPI_GELU_ERF_LNFOLD>(g, tile, num_cus, s); return;
     case EPI_GELU_TANH_LNFOLD: launch_tile_fold<EPI_GELU_TANH_LNFOLD>(g, tile, num_cus, s); return;
+    case EPI_ATTN_BIAS: launch_t<X6p0, EPI_ATTN_BIAS>(g, num_cus, s); return;
+    case EPI_ATTN_LNFOLD: launch_t<X6p0, EPI_ATTN_LNFOLD>(g, num_cus, s); return;
     default: launch_tile<EPI_BIAS>(g, tile, num_cus, s); return;
   }
 }
@@ -951,7 +1033,8 @@ int mq_debug_gemm_x6p_ln(const float* A, const void* W3, const float* bias, cons
   } else {
     MQ_CHECK_ARG(epi_is_lnfold(epi), "epi must be a LayerNorm-fold kind (got %d)", epi);
     MQ_CHECK_ARG(stats_in && s_fold, "consumer: NULL buffer");
-    MQ_CHECK_ARG(K == kLnPartW * kLnMaxParts, "consumer: K must be %d (got %d)", kLnPartW * kLnMaxParts, K);
+    // (the encoder's consumers run at K = 768, the width the partials describe; the epilogue's
+    // arithmetic takes the [M][8] partials as they are at any K)
   }
   int dev = 0, cus = 256;
   (void)hipGetDevice(&dev);
@@ -964,6 +1047,35 @@ int mq_debug_gemm_x6p_ln(const float* A, const void* W3, const float* bias, cons
   a.lf.s = s_fold;
   a.lf.eps = eps;
   launch_gemm_x6p(a, epi, tile, cus, (hipStream_t)stream);
+  MQ_HIP(hipGetLastError());
+  return MQ_OK;
+}
+
+int mq_debug_gemm_x6p_attn(const float* A, const void* W3, const float* bias, const int* mask, float* ctx, int M,
+                           int K, int heads, float scale, int epi, const float* stats_in, const float* s_fold,
+                           float eps, int max_workgroups, void* stream) {
+  using namespace mq;
+  clear_error();
+  MQ_CHECK_ARG(A && W3 && bias && mask && ctx, "NULL buffer");
+  MQ_CHECK_ARG(M > 0 && M % 32 == 0 && K > 0 && K % 32 == 0 && heads > 0 && heads <= 1024,
+               "bad shape M=%d K=%d heads=%d (M and K must be multiples of 32)", M, K, heads);
+  MQ_CHECK_ARG((int64_t)M * heads * 64 < (1ll << 31) && (int64_t)M * K < (1ll << 29), "M too large");
+  MQ_CHECK_ARG(epi == EPI_ATTN_BIAS || epi == EPI_ATTN_LNFOLD, "epi must be an attention kind (got %d)", epi);
+  MQ_CHECK_ARG(epi != EPI_ATTN_LNFOLD || (stats_in && s_fold), "fold: NULL buffer");
+  MQ_CHECK_ARG(max_workgroups >= 0 && max_workgroups % 8 == 0,
+               "max_workgroups must be 0 or a multiple of 8 (got %d)", max_workgroups);
+  int dev = 0, cus = 256;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  const int H = 64 * heads;
+  X6pArgs a{A, K, W3, bias, nullptr, 0, ctx, H, M, 3 * H, K};
+  a.lf.stats_in = stats_in;
+  a.lf.s = s_fold;
+  a.lf.eps = eps;
+  a.at.mask = mask;
+  a.at.scale = scale;
+  a.max_wg = max_workgroups;
+  launch_gemm_x6p(a, epi, 0, cus, (hipStream_t)stream);
   MQ_HIP(hipGetLastError());
   return MQ_OK;
 }

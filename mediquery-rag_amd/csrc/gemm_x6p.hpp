@@ -98,6 +98,11 @@ struct LnFold {
 void launch_ln_fold_weight(const float* W, const float* bias, const float* g, const float* b, int N, int K, float* Wg,
                            float* s_out, float* c_out, hipStream_t s);
 
+struct AttnEpi {
+  const int* mask = nullptr;
+  float scale = 0.f;
+};
+
 struct X6pArgs {
   const float* A;  // [M][lda] fp32 activations
   int lda;
@@ -110,7 +115,17 @@ struct X6pArgs {
   int M, N, K;  // K % 16 == 0
   int rx = -1;  // tile-walk region split (gemm_x6p.hip x6p_pick_rx): -1 = the pick, 0 = none, 1/2/4/8
   LnFold lf{};  // the EPI_RESID_LN_STATS / EPI_*_LNFOLD epilogues
+  // EPI_ATTN_BIAS / EPI_ATTN_LNFOLD (L = 32 attention in the QKV epilogue; tile 0 only): N = 3 H,
+  // H = 64 heads, M a multiple of 32, `out` is ctx [M][ldo], mask [M] int32, scale on Q
+  AttnEpi at{};
+  int max_wg = 0;  // > 0 (a multiple of 8): at most this many workgroups (tests: long tile walks)
 };
+
+// The attention of EPI_ATTN_* as a launch of its own, from a qkv [M][3 H] buffer that an unfused
+// QKV launch wrote (the forward's re-split path, MQ_ENC_OPT_X6_PRESPLIT 0): the same function on
+// the same values in the same register layout, so ctx [M][H] holds the epilogue's bits.  M % 32
+// == 0, H % 64 == 0.
+void launch_attn32(const float* qkv, const int* mask, float* ctx, int M, int H, float scale, hipStream_t s);
 
 // Tile shapes (workgroups of 8 waves, one per CU): 0 = 128 x 192 (4 compute + 4 loader
 // waves; the default: M = 8192 at N = 768 / 1536 / 2304 / 3072 gives whole rounds of 256

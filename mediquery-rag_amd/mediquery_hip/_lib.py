@@ -33,6 +33,7 @@ MQ_ENC_OPT_X6_PRESPLIT = 9
 MQ_ENC_OPT_ROWS_PLANES = 10
 MQ_ENC_OPT_LN_FOLD = 11
 MQ_ENC_OPT_CLS_KFREE = 12
+MQ_ENC_OPT_QKV_ATTN = 13
 
 
 class MQError(RuntimeError):
@@ -129,6 +130,7 @@ SIGNATURES = {
     "mq_debug_gemm_x6p": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "mq_debug_gemm_x6p_ln": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_float, _P]),
     "mq_debug_ln_fold_weight": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "mq_debug_gemm_x6p_attn": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _P, _P, ctypes.c_float, _I, _P]),
     "mq_debug_attention": (_I, [_P, _P, _I, _I, _I, _I, ctypes.c_float, _I, _P, _P]),
     "mq_debug_cls_attention": (_I, [_P, _P, _P, _P, _P, ctypes.c_float, _P, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P,
                                     _P, _P]),

@@ -309,7 +309,7 @@ class Encoder:
                "splitk_tiles": _lib.MQ_ENC_OPT_SPLITK_TILES, "ln_on_load": _lib.MQ_ENC_OPT_LN_ON_LOAD,
                "resident_layers": _lib.MQ_ENC_OPT_RESIDENT_LAYERS, "x6_presplit": _lib.MQ_ENC_OPT_X6_PRESPLIT,
                "rows_planes": _lib.MQ_ENC_OPT_ROWS_PLANES, "ln_fold": _lib.MQ_ENC_OPT_LN_FOLD,
-               "cls_kfree": _lib.MQ_ENC_OPT_CLS_KFREE}
+               "cls_kfree": _lib.MQ_ENC_OPT_CLS_KFREE, "qkv_attn": _lib.MQ_ENC_OPT_QKV_ATTN}
 
     def set_option(self, name, value):
         """Tuning option of the forward (mq_encoder_set_option): rows_max, rows_splits,
@@ -322,7 +322,9 @@ class Encoder:
         rows_planes (few-row forward: 0, default, merges the two-addend hand-offs into one plane
         by atomic adds; 1 = two planes; bit-identical), cls_kfree (CLS pooling, batched forward:
         1, default, the last layer attends from the CLS query without projecting K and V; 0 =
-        the all-token K / V projection and the attention kernel; equal to rounding)."""
+        the all-token K / V projection and the attention kernel; equal to rounding), qkv_attn
+        (split-f32 precision, batched forward, L == 32: 1, default, the attention runs in the
+        QKV GEMM's epilogue; 0 = the QKV launch and the attention launch; equal to rounding)."""
         _lib.call("mq_encoder_set_option", self._h, self.OPTIONS[name], int(value))
 
     def get_option(self, name):

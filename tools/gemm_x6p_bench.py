@@ -173,13 +173,79 @@ def ln_fold(a, dev, st):
             out_f.flush()
 
 
+def attn(a, dev, st):
+    """--attn: at M = 8192 (256 sequences of 32), K = 768, heads = 12, the QKV launch whose
+    epilogue is the attention (mq_debug_gemm_x6p_attn) against the QKV launch + the attention
+    launch (mq_debug_gemm_x6p or, with --ln-fold, _ln epi 6; then mq_debug_attention variant
+    12), alternating `--reps` times; one JSON line with every round's us and the medians."""
+    M, K, heads, L = 8192, 768, 12, 32
+    H, N = 64 * heads, 3 * 64 * heads
+    g = torch.Generator(device=dev).manual_seed(1)
+    A = torch.randn(M, K, device=dev, generator=g)
+    W = torch.randn(N, K, device=dev, generator=g) * 0.05
+    b = torch.randn(N, device=dev, generator=g)
+    mask = torch.ones(M, dtype=torch.int32, device=dev)
+    mask.view(-1, L)[::3, 20:] = 0
+    qkv = torch.empty(M, N, device=dev)
+    ctx_two = torch.empty(M, H, device=dev)
+    ctx_fused = torch.empty(M, H, device=dev)
+    s_fold = torch.randn(N, device=dev, generator=g) * 0.1
+    stats_in = torch.zeros(M, 8, 2, device=dev)
+    stats_in[:, :, 1] = 96.0
+    w3 = torch.empty(_lib.lib().mq_debug_w3_bytes(N, K), dtype=torch.uint8, device=dev)
+    _lib.call("mq_debug_split_w3", _lib.ptr(W), N, K, _lib.ptr(w3), st)
+    epi = 10 if a.ln_fold else 9
+
+    def two():
+        if a.ln_fold:
+            _lib.call("mq_debug_gemm_x6p_ln", _lib.ptr(A), _lib.ptr(w3), _lib.ptr(b), None, _lib.ptr(qkv), M, N, K, 6,
+                      0, _lib.ptr(stats_in), None, None, None, _lib.ptr(s_fold), 1e-12, st)
+        else:
+            _lib.call("mq_debug_gemm_x6p", _lib.ptr(A), _lib.ptr(w3), _lib.ptr(b), None, _lib.ptr(qkv), M, N, K, 0, 0,
+                      st)
+        _lib.call("mq_debug_attention", _lib.ptr(qkv), _lib.ptr(mask), M // L, L, H, heads, 0.125, 12,
+                  _lib.ptr(ctx_two), st)
+
+    def fused():
+        _lib.call("mq_debug_gemm_x6p_attn", _lib.ptr(A), _lib.ptr(w3), _lib.ptr(b), _lib.ptr(mask),
+                  _lib.ptr(ctx_fused), M, K, heads, 0.125, epi, _lib.ptr(stats_in), _lib.ptr(s_fold), 1e-12, 0, st)
+
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    rounds = {"two": [], "fused": []}
+    for fn in (two, fused):
+        for _ in range(a.iters):  # (a whole untimed round: the clock settles)
+            fn()
+    torch.cuda.synchronize()
+    diff = float((ctx_two - ctx_fused).abs().max())
+    for _ in range(a.reps):
+        for key, fn in (("two", two), ("fused", fused)):
+            e0.record()
+            for _ in range(a.iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            rounds[key].append(round(e0.elapsed_time(e1) * 1000.0 / a.iters, 2))
+    med = {k: sorted(v)[len(v) // 2] for k, v in rounds.items()}
+    line = json.dumps({"shape": "qkv_attn", "M": M, "K": K, "heads": heads, "epi": epi, "two_us": rounds["two"],
+                       "fused_us": rounds["fused"], "two_med": med["two"], "fused_med": med["fused"],
+                       "two_minus_fused_us": round(med["two"] - med["fused"], 2),
+                       "max_abs_diff_ctx": diff})
+    print(line, flush=True)
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--attn", action="store_true",
+                    help="the QKV launch with the attention epilogue vs QKV + attention launches (see attn()); "
+                         "with --ln-fold: the folded kinds")
     ap.add_argument("--ln-fold", action="store_true",
                     help="plain vs LayerNorm-fold epilogue per shape (see ln_fold()); with --ab: the pairs on the "
                          "LayerNorm-fold epilogues")
     ap.add_argument("--ab", default="", help="OLD:NEW tile code pairs to time alternating (see ab())")
-    ap.add_argument("--out", default="", help="--ab: also append the JSON lines to this file")
+    ap.add_argument("--out", default="", help="--ab / --attn: also append the JSON lines to this file")
     ap.add_argument("--check", action="store_true", help="--ab: bias epilogue, report max |err| vs float64")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--shapes", default=",".join(SHAPES))
@@ -191,6 +257,9 @@ def main():
     REPS = a.reps
     dev = torch.device("cuda", 0)
     st = _lib.stream_handle()
+    if a.attn:
+        attn(a, dev, st)
+        return
     if a.ab:
         ab(a, dev, st)
         return
