@@ -566,6 +566,44 @@ int mq_debug_cls_attention(const float* q, const float* x, const float* stats, c
 int mq_debug_attn_oproj(const float* qkv, const int* mask, int B, int L, int H, int heads, float scale,
                         const float* Wo, const float* bo, const float* resid, int cls_only, int hg, int qf,
                         int acc, float* out, void* stream);
+/* One few-row GEMM launch (K2r, rows_gemm_kernel: the product's kernel and launchers, unchanged)
+ * on device buffers, with the arguments forward_rows passes for the launch `kind` names:
+ *   MQ_ROWS_QKV    out = LN(a) W^T + bias.  a [M][K] = the sum of s_in (1..4) row-major planes
+ *                  of A, a_plane floats apart, or (s_in 0) the embedding sum A[ids[r]] +
+ *                  pos[r % L] + typ[types[r]] with A the word table [vocab][K], ids / types
+ *                  clamped into range (types NULL: row 0).  variant 0: out [M][N] row-major;
+ *                  variant 1: out in frag16 with the last third of the columns (V) as V^T blocks
+ *                  (N % 48 == 0).  ln_out (may be NULL) [M][K] gets LN(a).
+ *   MQ_ROWS_UP     out = GELU(LN(a) W^T + bias) in frag16; variant 0 erf, 1 tanh; s_in 1..4.
+ *   MQ_ROWS_OPROJ  out [M][N] = A W^T + bias + resid, A row-major with row stride lda, resid with
+ *                  row stride ldr (forward_rows passes L * H for both on the CLS-only layer).
+ *   MQ_ROWS_DOWN   A [M][K] given in frag16 (K columns); variant 0: `splits` (1..4) planes
+ *                  [M][N], o_plane floats apart, plane z = A[:, Kz] W[:, Kz]^T (+ bias + resid
+ *                  for z = 0); variant 1: the two planes added into ONE plane, zeroed here first
+ *                  (splits == 2).
+ * frag16 of a [R][C] matrix: 16 x 16 blocks, column block fastest, 256 floats each; element (r, c)
+ * of a block at float ((r + 16 (c >> 2)) * 4 + (c & 3)); a V^T block holds its transpose.  A
+ * frag16 buffer spans whole 16-row blocks; rows >= M of the last block are neither read into
+ * rows < M nor written.  W is [N][K] row-major: the hook builds its frag16 image.  The LN kinds
+ * need K = hidden in 256 / 512 / 768 / 1024 and splits 1; every kind K % (256 splits) == 0 with a
+ * per-split depth K / splits / 256 in {1, 2, 3, 4, 6, 8, 12, 16}; 1 <= M <= 256, N % 16 == 0.
+ * nt_w 0 / 1: weights loaded with the default / the non-temporal policy.  zbuf (may be NULL):
+ * zn floats (zn % 4 == 0) the launch zeroes beside its own work.  Arguments a kind does not
+ * read are ignored.  Allocates W's image: synchronous. */
+enum { MQ_ROWS_QKV = 0, MQ_ROWS_UP = 1, MQ_ROWS_OPROJ = 2, MQ_ROWS_DOWN = 3 };
+int mq_debug_rows_gemm(int kind, int variant, const float* A, int lda, int64_t a_plane, int s_in, const float* W,
+                       const float* bias, const float* resid, int ldr, float* out, int64_t o_plane, int M, int N,
+                       int K, int splits, const float* ln_g, const float* ln_b, float eps, float* ln_out,
+                       const int* ids, const int* types, int L, int vocab, const float* pos, const float* typ,
+                       int type_vocab, int nt_w, float* zbuf, int64_t zn, void* stream);
+/* One launch of the few-row forward's tail (ln_pool_kernel, unchanged): out [B][H] = the pooled,
+ * L2-normalised (raw != 0: not normalised) rows of LN(sum of `planes` (1..4) planes of hs,
+ * `plane` floats apart; ln_g, ln_b, eps).  hs holds `rows` rows per sequence: L ([B*L][H]), or 1
+ * with CLS pooling (the compact [B][H] CLS rows of a CLS-only last layer).  MQ_POOL_CLS takes
+ * row 0 of each sequence; MQ_POOL_MEAN the mean over the rows with mask [B*L] != 0 (none: 0).
+ * H 256 / 512 / 768 / 1024.  Asynchronous on `stream`. */
+int mq_debug_ln_pool(const float* hs, int planes, int64_t plane, const int* mask, int B, int L, int rows, int pooling,
+                     const float* ln_g, const float* ln_b, float eps, int H, float* out, int raw, void* stream);
 
 /* One launch of the cross-encoder head (K13, cls_head_kernel: the product's kernel, unchanged)
  * on device buffers: logits [B][n_labels] = cls_w tanh(pooler_w cls_b + pooler_b) + cls_b for

@@ -3219,6 +3219,25 @@ __global__ __launch_bounds__(256) void frag16_qkv_image_kernel(const float* __re
   img[frag16_offset(irow, icol, ld)] = qkv[idx];
 }
 
+// mq_debug_rows_gemm's LayerNorm-input kinds: the launches of forward_rows, by hidden size
+// (kind 0 QKV: variant 1 = frag16 output with V^T blocks; kind 1 FFN-up: variant 1 = tanh GELU)
+template <int VPL>
+void debug_rows_ln(int kind, int variant, const RowsArgs& g, int s_in, const float* lg, const float* lb, float eps,
+                   float* ln_out, hipStream_t s) {
+  if (kind == 0) {
+    if (variant)
+      launch_rows_ln<EPI_BIAS, VPL, FL_O | FL_OT>(g, s_in, lg, lb, eps, ln_out, s);
+    else
+      launch_rows_ln<EPI_BIAS, VPL>(g, s_in, lg, lb, eps, ln_out, s);
+  } else if (variant) {
+    launch_rows_ln<EPI_GELU_TANH, VPL, FL_O>(g, s_in, lg, lb, eps, ln_out, s);
+  } else {
+    launch_rows_ln<EPI_GELU_ERF, VPL, FL_O>(g, s_in, lg, lb, eps, ln_out, s);
+  }
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 }  // namespace
 
 extern "C" {
@@ -3447,6 +3466,135 @@ int mq_debug_attn_oproj(const float* qkv, const int* mask, int B, int L, int H, 
   (void)hipFree(scratch);
   if (err == hipSuccess) err = serr;
   if (err != hipSuccess) MQ_FAIL(MQ_EHIP, "fused attention + output projection failed: %s", hipGetErrorString(err));
+  return MQ_OK;
+}
+
+int mq_debug_rows_gemm(int kind, int variant, const float* A, int lda, int64_t a_plane, int s_in, const float* W,
+                       const float* bias, const float* resid, int ldr, float* out, int64_t o_plane, int M, int N,
+                       int K, int splits, const float* ln_g, const float* ln_b, float eps, float* ln_out,
+                       const int* ids, const int* types, int L, int vocab, const float* pos, const float* typ,
+                       int type_vocab, int nt_w, float* zbuf, int64_t zn, void* stream) {
+  clear_error();
+  MQ_CHECK_ARG(kind >= MQ_ROWS_QKV && kind <= MQ_ROWS_DOWN, "bad kind %d", kind);
+  MQ_CHECK_ARG(variant == 0 || variant == 1, "variant must be 0 or 1 (got %d)", variant);
+  MQ_CHECK_ARG(A && W && bias && out, "NULL buffer");
+  MQ_CHECK_ARG(M >= 1 && M <= kRowsMax, "M must be in [1, %d] (got %d)", kRowsMax, M);
+  const bool ln_kind = kind == MQ_ROWS_QKV || kind == MQ_ROWS_UP;
+  const bool vt = kind == MQ_ROWS_QKV && variant;
+  MQ_CHECK_ARG(N > 0 && N % kRT == 0 && (!vt || N % 48 == 0), "N must be a positive multiple of %d (got %d)",
+               vt ? 48 : kRT, N);
+  MQ_CHECK_ARG(splits >= 1 && splits <= 4, "splits must be in [1, 4] (got %d)", splits);
+  MQ_CHECK_ARG(K > 0 && K % (256 * splits) == 0, "K must be a positive multiple of 256 * splits (K %d, splits %d)", K,
+               splits);
+  MQ_CHECK_ARG(rows_nb_ok(K / splits / 256), "no kernel for a per-split depth of %d (K %d, splits %d)", K / splits, K,
+               splits);
+  MQ_CHECK_ARG((int64_t)N * K * 4 < ((int64_t)1 << 31), "W is past the 2 GB a buffer load addresses");
+  MQ_CHECK_ARG(nt_w == 0 || nt_w == 1, "nt_w must be 0 or 1 (got %d)", nt_w);
+  MQ_CHECK_ARG(zn >= 0 && zn % 4 == 0 && (zn == 0 || zbuf) && aligned16(zbuf),
+               "zbuf must be 16-byte aligned with zn %% 4 == 0 (zn %lld)", (long long)zn);
+  MQ_CHECK_ARG(aligned16(A) && aligned16(W), "A and W must be 16-byte aligned");
+  const bool acc = kind == MQ_ROWS_DOWN && variant;
+  if (ln_kind) {
+    MQ_CHECK_ARG(K == 256 || K == 512 || K == 768 || K == 1024,
+                 "a LayerNorm input needs K = hidden in 256 / 512 / 768 / 1024 (got %d)", K);
+    MQ_CHECK_ARG(splits == 1, "a LayerNorm input takes an unsplit K (splits %d)", splits);
+    MQ_CHECK_ARG(ln_g && ln_b && aligned16(ln_g) && aligned16(ln_b), "NULL or unaligned LayerNorm weights");
+    MQ_CHECK_ARG(!ln_out || aligned16(ln_out), "ln_out must be 16-byte aligned");
+    MQ_CHECK_ARG(s_in >= (kind == MQ_ROWS_QKV ? 0 : 1) && s_in <= 4, "s_in out of range (kind %d, s_in %d)", kind,
+                 s_in);
+    if (s_in == 0) {
+      MQ_CHECK_ARG(ids && pos && typ && aligned16(pos) && aligned16(typ), "the embedding gather needs ids, pos, typ");
+      MQ_CHECK_ARG(L >= 1 && vocab >= 1 && type_vocab >= 1, "bad gather shape L=%d vocab=%d type_vocab=%d", L, vocab,
+                   type_vocab);
+    } else {
+      MQ_CHECK_ARG(a_plane >= 0 && a_plane % 4 == 0, "a_plane must be a non-negative multiple of 4 (got %lld)",
+                   (long long)a_plane);
+    }
+  } else {
+    MQ_CHECK_ARG(resid && ldr >= N, "the residual kinds need resid with ldr >= N (ldr %d)", ldr);
+    if (kind == MQ_ROWS_OPROJ) {
+      MQ_CHECK_ARG(splits == 1, "oproj takes an unsplit K (splits %d)", splits);
+      MQ_CHECK_ARG(lda >= K && lda % 4 == 0, "lda must be a multiple of 4, >= K (lda %d, K %d)", lda, K);
+    } else {
+      MQ_CHECK_ARG(!acc || splits == 2, "acc needs exactly two K splits (got %d)", splits);
+      MQ_CHECK_ARG(acc || splits == 1 || o_plane >= (int64_t)M * N, "o_plane must hold a plane of M * N floats (got %lld)",
+                   (long long)o_plane);
+    }
+  }
+  hipStream_t s = (hipStream_t)stream;
+  float* wimg = nullptr;  // W's frag16 image
+  const size_t w_floats = (size_t)N * K;
+  if (hipMalloc((void**)&wimg, w_floats * 4) != hipSuccess) MQ_FAIL(MQ_ENOMEM, "operand image allocation failed");
+  hipLaunchKernelGGL(frag16_image_kernel, dim3((unsigned)((w_floats / 4 + 255) / 256)), dim3(256), 0, s, W, N, K,
+                     reinterpret_cast<floatx4*>(wimg));
+  hipError_t err = hipSuccess;
+  if (acc) err = hipMemsetAsync(out, 0, (size_t)M * N * 4, s);
+  if (err == hipSuccess) {  // lda / ldw / ldo as forward_rows passes them: K, K (oproj: the caller's lda), N
+    RowsArgs g{A, kind == MQ_ROWS_OPROJ ? lda : K, ln_kind && s_in ? a_plane : 0, wimg, K, bias,
+               ln_kind ? nullptr : resid, ln_kind ? 0 : ldr, out, N, kind == MQ_ROWS_DOWN ? o_plane : 0, M, N, K, splits};
+    g.nt_w = nt_w;
+    g.zbuf = zn ? zbuf : nullptr;
+    g.zn = zn;
+    if (ln_kind && s_in == 0) {
+      g.ids = ids;
+      g.L = L;
+      g.vocab = vocab;
+      g.pos = pos;
+      g.typ = typ;
+      g.types = types;
+      g.type_vocab = type_vocab;
+    }
+    if (ln_kind) {
+      switch (K) {
+        case 256: debug_rows_ln<1>(kind, variant, g, s_in, ln_g, ln_b, eps, ln_out, s); break;
+        case 512: debug_rows_ln<2>(kind, variant, g, s_in, ln_g, ln_b, eps, ln_out, s); break;
+        case 768: debug_rows_ln<3>(kind, variant, g, s_in, ln_g, ln_b, eps, ln_out, s); break;
+        default: debug_rows_ln<4>(kind, variant, g, s_in, ln_g, ln_b, eps, ln_out, s); break;
+      }
+    } else if (kind == MQ_ROWS_OPROJ) {
+      launch_rows<EPI_RESID>(g, s);
+    } else if (acc) {
+      launch_rows<EPI_RESID, FL_A | FL_ACC>(g, s);
+    } else {
+      launch_rows<EPI_RESID, FL_A>(g, s);
+    }
+    err = hipGetLastError();
+  }
+  const hipError_t serr = hipStreamSynchronize(s);
+  (void)hipFree(wimg);
+  if (err == hipSuccess) err = serr;
+  if (err != hipSuccess) MQ_FAIL(MQ_EHIP, "few-row GEMM failed: %s", hipGetErrorString(err));
+  return MQ_OK;
+}
+
+int mq_debug_ln_pool(const float* hs, int planes, int64_t plane, const int* mask, int B, int L, int rows, int pooling,
+                     const float* ln_g, const float* ln_b, float eps, int H, float* out, int raw, void* stream) {
+  clear_error();
+  MQ_CHECK_ARG(hs && ln_g && ln_b && out, "NULL buffer");
+  MQ_CHECK_ARG(H == 256 || H == 512 || H == 768 || H == 1024, "hidden must be 256/512/768/1024 (got %d)", H);
+  MQ_CHECK_ARG(B >= 1 && L >= 1, "bad shape B=%d L=%d", B, L);
+  MQ_CHECK_ARG(planes >= 1 && planes <= 4, "planes must be in [1, 4] (got %d)", planes);
+  MQ_CHECK_ARG(planes == 1 || (plane > 0 && plane % 4 == 0), "plane must be a positive multiple of 4 (got %lld)",
+               (long long)plane);
+  MQ_CHECK_ARG(pooling == MQ_POOL_CLS || pooling == MQ_POOL_MEAN, "bad pooling %d", pooling);
+  MQ_CHECK_ARG(rows == L || (rows == 1 && pooling == MQ_POOL_CLS),
+               "rows per sequence must be L, or 1 with CLS pooling (rows %d, L %d)", rows, L);
+  MQ_CHECK_ARG(pooling == MQ_POOL_CLS || mask, "mean pooling needs the mask");
+  MQ_CHECK_ARG(raw == 0 || raw == 1, "raw must be 0 or 1 (got %d)", raw);
+  MQ_CHECK_ARG(aligned16(hs) && aligned16(ln_g) && aligned16(ln_b) && aligned16(out), "buffers must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)((B + 3) / 4));
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, hs, planes, plane, mask, B, L, rows, pooling, ln_g, ln_b, eps, out,
+                       raw);
+  };
+  switch (H) {
+    case 256: go(ln_pool_kernel<1>); break;
+    case 512: go(ln_pool_kernel<2>); break;
+    case 768: go(ln_pool_kernel<3>); break;
+    default: go(ln_pool_kernel<4>); break;
+  }
+  MQ_HIP(hipGetLastError());
   return MQ_OK;
 }
 

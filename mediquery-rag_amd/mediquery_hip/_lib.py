@@ -34,6 +34,7 @@ MQ_ENC_OPT_ROWS_PLANES = 10
 MQ_ENC_OPT_LN_FOLD = 11
 MQ_ENC_OPT_CLS_KFREE = 12
 MQ_ENC_OPT_QKV_ATTN = 13
+MQ_ROWS_QKV, MQ_ROWS_UP, MQ_ROWS_OPROJ, MQ_ROWS_DOWN = 0, 1, 2, 3  # mq_debug_rows_gemm kinds
 
 
 class MQError(RuntimeError):
@@ -135,6 +136,9 @@ SIGNATURES = {
     "mq_debug_cls_attention": (_I, [_P, _P, _P, _P, _P, ctypes.c_float, _P, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P,
                                     _P, _P]),
     "mq_debug_attn_oproj": (_I, [_P, _P, _I, _I, _I, _I, ctypes.c_float, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "mq_debug_rows_gemm": (_I, [_I, _I, _P, _I, _I64, _I, _P, _P, _P, _I, _P, _I64, _I, _I, _I, _I, _P, _P,
+                                ctypes.c_float, _P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _I64, _P]),
+    "mq_debug_ln_pool": (_I, [_P, _I, _I64, _P, _I, _I, _I, _I, _P, _P, ctypes.c_float, _I, _P, _I, _P]),
     "mq_debug_int8_screen":(_I, [_P, _P, _I, _P, _P, _P]),
 }
 
