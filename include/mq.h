@@ -227,6 +227,64 @@ int mq_mask_contains(const uint8_t* text, int64_t text_bytes, const int64_t* off
                      const uint8_t* pattern, int pattern_len, int negate, uint32_t* bits, int mode,
                      uint32_t* scratch, void* stream);
 
+/* Lexical retrieval: Okapi BM25 over a device mirror of the documents' token ids, brute force
+ * (no inverted index), as the flat index and mq_mask_contains are; it replaces LangChain's
+ * BM25Retriever next to the dense search (EnsembleRetriever, fused by reciprocal rank on the
+ * host: vectorstore.py).  The definition:
+ *   terms    a row's terms are its body token ids (the tokenizer's ids without [CLS] / [SEP]),
+ *            stored as uint16.  ngram = 1: a term key is the id; ngram = 2: a term key is
+ *            (id[i] << 16) | id[i + 1] for adjacent tokens of one row (never across a row
+ *            start), so a row of L tokens has max(L - 1, 0) terms.
+ *   stats    over ALL n rows (masked-out and zero-length rows count): N = n, dl_r = the number
+ *            of terms of row r, avgdl = sum dl_r / N, df_t = the rows holding term t.
+ *   score    Lucene's non-negative idf with the classic numerator; for the query's distinct
+ *            terms t with query counts qf_t:
+ *              idf_t   = ln(1 + (N - df_t + 0.5) / (df_t + 0.5))
+ *              w_t     = qf_t (k1 + 1) idf_t                    host, float64, rounded to fp32
+ *              c0, c1  = k1 (1 - b),  k1 b / avgdl              host, float64, rounded to fp32
+ *              score_r = sum_t w_t tf_rt / (tf_rt + c0 + c1 dl_r)      device, fp32
+ *            tf_rt is an exact integer count.  The device sums the terms with tf_rt > 0 in slot
+ *            order (the order of `keys`), every operation rounded to nearest and never
+ *            contracted, written once below as MQ_LEX_NORM / MQ_LEX_TERM over the caller's
+ *            rounding primitives: two rows with equal counts and equal dl score bitwise equal.
+ *   result   only rows with at least one query term (sum tf > 0) that the mask admits are
+ *            candidates; ordered by (score desc, row id asc), padded with (-inf, -1).
+ * A caller with more than MQ_LEX_MAX_TERMS distinct query terms computes df for all of them in
+ * chunks and keeps the MQ_LEX_MAX_TERMS with the largest idf (ties to the smaller key).
+ *   tokens   device uint16 [n_tokens], the rows' token ids concatenated, 16-byte aligned; only
+ *            [0, n_tokens) is read.  May be NULL when n_tokens == 0.
+ *   offsets  device int64 [n + 1] counted in tokens, non-decreasing, offsets[0] == 0,
+ *            offsets[n] == n_tokens (zero-length rows allowed).  The kernel trusts them but
+ *            reads no token outside [0, n_tokens) and counts into its own rows only.
+ *   keys, w  HOST arrays of n_terms distinct keys / their weights, passed to the kernel by
+ *            value (1 <= n_terms <= MQ_LEX_MAX_TERMS).
+ *   bits     device row mask (bit r % 32 of word r / 32, >= ceil(n / 32) words) or NULL = all.
+ *   scratch  device, mq_lex_scratch_bytes(n, k) bytes (k = MQ_MAX_K serves every k; mq_lex_df
+ *            needs mq_lex_scratch_bytes(n, 1)), 16-byte aligned; neither call allocates or
+ *            frees device memory; not one of the outputs.
+ * lex_scan_kernel (K14): a workgroup owns blocks of 64 consecutive rows, whose tokens are one
+ * contiguous stretch of the blob; it streams the stretch position-parallel (16-byte loads, 8
+ * tokens a lane), probes an open-addressed hash of the query's keys in LDS per position, and on
+ * a hit adds 1 to an integer LDS counter tf[row][slot].  mq_lex_df counts per block and slot
+ * the rows with tf > 0 and adds them with one integer global atomic each; it is synchronous
+ * (df is a host array of n_terms counts).  mq_lex_topk scores the block's rows, one lane a
+ * row, keeps a sorted running top-k per workgroup over a persistent grid and merges the
+ * workgroups' lists with mq_topk_merge_device; out_scores [k] / out_ids [k] are both device
+ * (io_on_device = 1, asynchronous on `stream`) or both host (synchronous).  n == 0 gives
+ * padding only.  Launches run on the GPU the buffers live on.  The argument checks (sizes,
+ * ngram, n_terms, distinct keys, k, NULL pointers with n > 0, alignment, scratch not an
+ * output) come before any HIP call. */
+#define MQ_LEX_MAX_TERMS 128
+#define MQ_LEX_NORM(fmul, fadd, c0, c1, dl) fadd((c0), fmul((c1), (dl)))
+#define MQ_LEX_TERM(fmul, fadd, fdiv, w, tf, norm) fdiv(fmul((w), (tf)), fadd((tf), (norm)))
+int64_t mq_lex_scratch_bytes(int64_t n, int k);
+int mq_lex_df(const uint16_t* tokens, int64_t n_tokens, const int64_t* offsets, int64_t n, int ngram,
+              const uint32_t* keys, int n_terms, int64_t* df, void* scratch, void* stream);
+int mq_lex_topk(const uint16_t* tokens, int64_t n_tokens, const int64_t* offsets, int64_t n, int ngram,
+                const uint32_t* keys, const float* w, int n_terms, float c0, float c1,
+                const uint32_t* bits, int k, float* out_scores, int64_t* out_ids, int io_on_device,
+                void* scratch, void* stream);
+
 /* Maximal marginal relevance (LangChain's maximal_marginal_relevance, the selection behind
  * VectorStore.max_marginal_relevance_search): from each query's candidate list pick k rows
  * greedily, trading similarity to the query against similarity to the rows already picked.

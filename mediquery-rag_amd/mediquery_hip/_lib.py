@@ -25,6 +25,7 @@ MQ_HEAD_MAX_LABELS = 8           # most labels a cross-encoder head carries (mq_
 MQ_MASK_SET, MQ_MASK_AND, MQ_MASK_OR, MQ_MASK_CLEAR = 0, 1, 2, 3
 MQ_CONTAINS_MAX_BYTES = 256      # longest mq_mask_contains pattern (UTF-8 bytes)
 MQ_CONTAINS_SPAN_BYTES = 16384   # text bytes one workgroup of the scan owns
+MQ_LEX_MAX_TERMS = 128           # most distinct query terms one mq_lex_df / mq_lex_topk call takes
 # mq_encoder_set_option ids (include/mq.h)
 MQ_ENC_OPT_ROWS_MAX, MQ_ENC_OPT_ROWS_SPLITS, MQ_ENC_OPT_SPLITK_MAX = 0, 1, 2
 MQ_ENC_OPT_LN_ROWS_PER_WAVE, MQ_ENC_OPT_FUSE_ATTN_OPROJ, MQ_ENC_OPT_FUSED_LN = 3, 4, 5
@@ -96,6 +97,10 @@ SIGNATURES = {
     "mq_mask_eval_bits": (_I, [_P, _I64, _P, _I, _P, _I, _P]),
     "mq_mask_combine": (_I, [_P, _P, _I64, _I, _P]),
     "mq_mask_contains": (_I, [_P, _I64, _P, _I64, _P, _I, _I, _P, _I, _P, _P]),
+    "mq_lex_scratch_bytes": (_I64, [_I64, _I]),
+    "mq_lex_df": (_I, [_P, _I64, _P, _I64, _I, _P, _I, _P, _P, _P]),
+    "mq_lex_topk": (_I, [_P, _I64, _P, _I64, _I, _P, _P, _I, ctypes.c_float, ctypes.c_float, _P, _I, _P, _P, _I,
+                         _P, _P]),
     "mq_index_search_masked": (_I, [_P, _P, _I, _P, _P, _P, _I, _P]),
     "mq_index_search_masked_batch": (_I, [_P, _P, _I64, _I, _P, _P, _P, _I, _P]),
     "mq_index_masked_gathers": (_I, [_P, ctypes.POINTER(_I64)]),

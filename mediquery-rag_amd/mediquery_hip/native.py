@@ -462,6 +462,86 @@ def mask_contains(text, offsets, pattern, bits, mode, negate=False, stream=None,
                   _lib.stream_handle(stream))
 
 
+def lex_scratch_bytes(n, k=_lib.MQ_MAX_K):
+    """Bytes of device scratch mq_lex_df / mq_lex_topk want for n rows and a top-k of k."""
+    return int(_lib.lib().mq_lex_scratch_bytes(int(n), int(k)))
+
+
+def _check_lex(tokens, offsets, ngram, keys, scratch, k):
+    """The device and size checks shared by lex_df / lex_topk -> (n, keys uint32, scratch)."""
+    import torch
+    if not (getattr(tokens, "is_cuda", False) and tokens.dtype == torch.uint16 and tokens.is_contiguous()
+            and tokens.dim() == 1):
+        raise ValueError("tokens must be a contiguous 1-d uint16 device tensor")
+    if tokens.numel() and tokens.data_ptr() % 16:
+        raise ValueError("tokens must start at a 16-byte aligned address")
+    if not (getattr(offsets, "is_cuda", False) and offsets.dtype == torch.int64 and offsets.is_contiguous()
+            and offsets.numel() >= 1 and offsets.device == tokens.device):
+        raise ValueError("offsets must be a contiguous int64 tensor of n + 1 elements on the tokens' device")
+    if ngram not in (1, 2):
+        raise ValueError("ngram must be 1 or 2 (got %r)" % (ngram,))
+    n = offsets.numel() - 1
+    keys = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1)
+    if not 1 <= keys.size <= _lib.MQ_LEX_MAX_TERMS:
+        raise ValueError("a call takes 1..%d terms (got %d)" % (_lib.MQ_LEX_MAX_TERMS, keys.size))
+    if np.unique(keys).size != keys.size:
+        raise ValueError("keys must be distinct")
+    need = lex_scratch_bytes(n, k)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=tokens.device)
+    if not (getattr(scratch, "is_cuda", False) and scratch.is_contiguous() and scratch.device == tokens.device
+            and scratch.numel() * scratch.element_size() >= need and scratch.data_ptr() % 16 == 0):
+        raise ValueError("scratch must be a contiguous 16-byte aligned tensor of >= %d bytes on the tokens' device"
+                         % need)
+    return n, keys, scratch
+
+
+def lex_df(tokens, offsets, ngram, keys, scratch=None, stream=None):
+    """Document frequencies int64 [n_terms] of the term keys over the token mirror (include/mq.h
+    mq_lex_df): tokens uint16 [n_tokens] = the rows' token ids concatenated, offsets int64
+    [n + 1] in tokens (torch, one device), keys 1..MQ_LEX_MAX_TERMS distinct uint32 (host).
+    scratch: lex_scratch_bytes(n, 1) bytes (None: a torch.empty of that size).  Synchronous."""
+    n, keys, scratch = _check_lex(tokens, offsets, ngram, keys, scratch, 1)
+    df = np.zeros(keys.size, dtype=np.int64)
+    with _lib.device_scope(tokens.device.index):
+        _lib.call("mq_lex_df", _lib.ptr(tokens) if tokens.numel() else None, tokens.numel(), _lib.ptr(offsets), n,
+                  int(ngram), _lib.ptr(keys), keys.size, _lib.ptr(df), _lib.ptr(scratch),
+                  _lib.stream_handle(stream))
+    return df
+
+
+def lex_topk(tokens, offsets, ngram, keys, w, c0, c1, k, bits=None, scratch=None, stream=None, out=None):
+    """BM25 top-k over the token mirror (include/mq.h mq_lex_topk): keys / w the query's distinct
+    term keys and their fp32 weights (host), c0, c1 the length normalisation, bits a device row
+    mask or None.  -> (scores f32 [k], ids int64 [k]) device tensors (`out`: a pair to write
+    into), best first, padded with (-inf, -1); asynchronous on `stream` (or the device's
+    current stream)."""
+    import torch
+    k = int(k)
+    if not 1 <= k <= _lib.MQ_MAX_K:
+        raise ValueError("k must be in [1, %d] (got %d)" % (_lib.MQ_MAX_K, k))
+    n, keys, scratch = _check_lex(tokens, offsets, ngram, keys, scratch, k)
+    w = np.ascontiguousarray(w, dtype=np.float32).reshape(-1)
+    if w.size != keys.size:
+        raise ValueError("%d keys, %d weights" % (keys.size, w.size))
+    if bits is not None:
+        check_mask_words(bits, n, tokens.device.index)
+    with _lib.device_scope(tokens.device.index):
+        if out is None:
+            out = (torch.empty(k, dtype=torch.float32, device=tokens.device),
+                   torch.empty(k, dtype=torch.int64, device=tokens.device))
+        s, i = out
+        if not (s.is_cuda and i.is_cuda and s.device == tokens.device and i.device == tokens.device
+                and s.dtype == torch.float32 and i.dtype == torch.int64 and s.numel() >= k and i.numel() >= k
+                and s.is_contiguous() and i.is_contiguous()):
+            raise ValueError("out must be (float32 [k], int64 [k]) contiguous tensors on the tokens' device")
+        _lib.call("mq_lex_topk", _lib.ptr(tokens) if tokens.numel() else None, tokens.numel(), _lib.ptr(offsets), n,
+                  int(ngram), _lib.ptr(keys), _lib.ptr(w), keys.size, ctypes.c_float(float(c0)),
+                  ctypes.c_float(float(c1)), _lib.ptr(bits), k, _lib.ptr(s), _lib.ptr(i), 1, _lib.ptr(scratch),
+                  _lib.stream_handle(stream))
+    return s, i
+
+
 def mask_combine(dst, src, mode, stream=None):
     """dst (mode)= src (None: all ones; MQ_MASK_CLEAR: zeros) on the device."""
     check_mask_words(dst, 0)

@@ -20,6 +20,13 @@ device row masks: `filter` / `where` over metadata code columns (`_MetaColumns`)
 `where_document` ($contains / $not_contains / $and / $or on the text) over a device mirror of
 the documents (`_TextMirror`, built at its first use; `_match_document` is the definition).
 
+Lexical and hybrid retrieval (LangChain's `BM25Retriever` and `EnsembleRetriever([bm25, dense])`):
+`lexical_search*` ranks the rows by BM25 over a device mirror of their token ids (`_TokenMirror`,
+mq_lex_df / mq_lex_topk; the definition is in include/mq.h), `hybrid_search*` fuses the dense
+and the lexical top fetch_k by weighted reciprocal rank (`rrf_fuse`, on the host), and
+`as_retriever(search_type="lexical" | "hybrid")` wraps them.  Both take `filter` and
+`where_document`.  Nothing of it is persisted: the mirror is derived from the documents.
+
 Persistence: `mq_<collection>.json` (ids, documents, metadatas, and the name of the slab
 file) is the base commit point; a full write (the first write, `delete`, an upsert that
 replaces rows, an explicit `persist()`) puts the rows in a fresh `mq_<collection>.<gen>.flat`
@@ -45,7 +52,8 @@ import numpy as np
 
 from . import _lib
 from .compat import Document, VectorStoreBase
-from .native import FlatIndex, mask_combine, mask_contains, mask_eval, mask_eval_bits
+from .native import (FlatIndex, lex_df, lex_scratch_bytes, lex_topk, mask_combine, mask_contains, mask_eval,
+                     mask_eval_bits)
 
 DEFAULT_K = 4  # LangChain VectorStore.similarity_search default; the reference passes k=5
 
@@ -365,6 +373,179 @@ class _TextMirror:
                       scratch=self.scratch)
 
 
+def body_tokens(tokenizer, texts):
+    """-> (flat uint16 token ids, int64 lengths [len(texts)]): each text's body tokens, what
+    `tokenizer(texts)` returns without [CLS] / [SEP] (so truncated as the tokenizer truncates),
+    concatenated.  An id past 65535 raises ValueError (the mirror stores uint16)."""
+    texts = list(texts)
+    if not texts:
+        return np.zeros(0, np.uint16), np.zeros(0, np.int64)
+    ids, mask = tokenizer(texts)
+    ids, mask = np.asarray(ids), np.asarray(mask)
+    lens = np.maximum(mask.sum(axis=1).astype(np.int64) - 2, 0)
+    cols = np.arange(ids.shape[1], dtype=np.int64)[None, :]
+    flat = ids[(cols >= 1) & (cols <= lens[:, None])]
+    if flat.size and (int(flat.max()) > 0xFFFF or int(flat.min()) < 0):
+        raise ValueError("lexical search stores token ids as uint16: the tokenizer's vocabulary must not "
+                         "exceed 65536 ids (got id %d)" % int(flat.max()))
+    return flat.astype(np.uint16), lens
+
+
+def term_keys(tokens, ngram):
+    """The uint32 term keys of one row's body tokens: the ids (ngram 1) or (id[i] << 16) | id[i + 1]
+    of adjacent tokens (ngram 2: max(L - 1, 0) terms)."""
+    t = np.asarray(tokens).astype(np.uint32)
+    if ngram == 1:
+        return t
+    return (t[:-1] << np.uint32(16)) | t[1:] if t.size > 1 else np.zeros(0, np.uint32)
+
+
+def bm25_plan(keys, qf, df, n_rows, avgdl, k1, b, max_terms=_lib.MQ_LEX_MAX_TERMS):
+    """The device call's arguments for one query (the definition: include/mq.h): the query's
+    distinct term keys with counts qf and document frequencies df over n_rows rows ->
+    (keys uint32, w float32, c0 float32, c1 float32), everything computed in float64 and rounded
+    once.  More than max_terms terms: the max_terms with the largest idf stay (ties to the
+    smaller key).  Slots are in ascending key order."""
+    keys = np.asarray(keys, dtype=np.uint32)
+    qf = np.asarray(qf, dtype=np.float64)
+    df = np.asarray(df, dtype=np.float64)
+    idf = np.log(1.0 + (float(n_rows) - df + 0.5) / (df + 0.5))
+    if keys.size > max_terms:
+        keep = np.sort(np.lexsort((keys, -idf))[:max_terms])  # by (-idf, key); back to key order
+        keys, qf, idf = keys[keep], qf[keep], idf[keep]
+    order = np.argsort(keys, kind="stable")
+    keys, qf, idf = keys[order], qf[order], idf[order]
+    w = (qf * (float(k1) + 1.0) * idf).astype(np.float32)
+    return keys, w, np.float32(float(k1) * (1.0 - float(b))), np.float32(float(k1) * float(b) / float(avgdl))
+
+
+def _check_rrf(weights, c):
+    try:
+        ws = [float(x) for x in weights]
+    except (TypeError, ValueError):
+        raise ValueError("weights must be two non-negative finite numbers, got %r" % (weights,))
+    if len(ws) != 2 or not all(math.isfinite(x) and x >= 0.0 for x in ws) or ws[0] + ws[1] <= 0.0:
+        raise ValueError("weights must be two non-negative finite numbers, not both zero, got %r" % (weights,))
+    if isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or c < 0:
+        raise ValueError("c must be a non-negative finite number, got %r" % (c,))
+    return ws, float(c)
+
+
+def rrf_fuse(dense_rows, lexical_rows, weights=(0.5, 0.5), c=60, k=None):
+    """LangChain's EnsembleRetriever.weighted_reciprocal_rank over two ranked lists of row ids:
+    rrf[row] = sum over the lists holding it of weight / (rank + c), rank from 1, in float64;
+    rows sorted by rrf descending with a stable sort over the order "dense list, then the
+    lexical rows not yet seen".  -> [(row, rrf)], the first k."""
+    ws, c = _check_rrf(weights, c)
+    rrf, order = {}, []
+    for rows, wt in ((dense_rows, ws[0]), (lexical_rows, ws[1])):
+        for rank, r in enumerate(rows, start=1):
+            r = int(r)
+            if r not in rrf:
+                rrf[r] = 0.0
+                order.append(r)
+            rrf[r] += wt / (rank + c)
+    order.sort(key=lambda r: rrf[r], reverse=True)  # stable; reverse keeps equal rows in order
+    out = [(r, rrf[r]) for r in order]
+    return out if k is None else out[:max(0, int(k))]
+
+
+class _TokenMirror:
+    """Device mirror of the documents for lexical search, the twin of `_TextMirror`: the rows'
+    body token ids concatenated (`blob`, uint16) and their int64 offsets [n + 1] in tokens, both
+    with capacity doubling, plus the scratch mq_lex_df / mq_lex_topk want.  Built at the first
+    lexical use, tokenising CHUNK texts at a time (the [n, L] id arrays of a whole corpus never
+    exist on the host); a plain append tokenises and uploads only the new rows; `epoch` tells
+    when the rows were renumbered and the mirror must be rebuilt.  `df` caches term key -> document
+    frequency for one store version.  Costs 2 bytes a token + 8 bytes a row of HBM."""
+    CHUNK = 4096
+
+    def __init__(self, device, epoch, tokenizer, ngram):
+        import torch
+        self.dev = torch.device("cuda", device)
+        self.epoch = epoch
+        self.version = -1
+        self.tokenizer = tokenizer
+        self.ngram = ngram
+        self.n = 0
+        self.n_tokens = 0
+        self.sum_dl = 0  # terms over all rows (avgdl = sum_dl / n)
+        self.df = {}
+        # int16 storage (every torch copy supports it), handed to the kernels as uint16 views
+        self.blob = torch.empty(0, dtype=torch.int16, device=self.dev)
+        self.offs = torch.zeros(1, dtype=torch.int64, device=self.dev)
+        self.scratch = torch.empty(lex_scratch_bytes(1 << 40, _lib.MQ_MAX_K), dtype=torch.uint8, device=self.dev)
+
+    def nbytes(self):
+        """HBM the mirror holds (allocated capacity, scratch included)."""
+        return self.blob.numel() * 2 + self.offs.numel() * 8 + self.scratch.numel()
+
+    def extend(self, texts):
+        """Append rows `texts` (the store's rows n .. n + len(texts)); drops the df cache."""
+        import torch
+        self.df = {}
+        for at in range(0, len(texts), self.CHUNK):
+            flat, lens = body_tokens(self.tokenizer, texts[at:at + self.CHUNK])
+            ends = self.n_tokens + np.cumsum(lens)
+            self.blob = _TextMirror._grown(self.blob, self.n_tokens, self.n_tokens + flat.size)
+            self.offs = _TextMirror._grown(self.offs, self.n + 1, self.n + 1 + lens.size)
+            if flat.size:
+                self.blob[self.n_tokens:self.n_tokens + flat.size] = torch.from_numpy(flat.view(np.int16)).to(self.dev)
+            self.offs[self.n + 1:self.n + 1 + lens.size] = torch.from_numpy(ends).to(self.dev)
+            self.n += int(lens.size)
+            self.n_tokens += int(flat.size)
+            self.sum_dl += int(lens.sum()) if self.ngram == 1 else int(np.maximum(lens - 1, 0).sum())
+
+    def _views(self):
+        import torch
+        return self.blob[:self.n_tokens].view(torch.uint16), self.offs[:self.n + 1]
+
+    def frequencies(self, keys):
+        """df of the uint32 term keys (distinct), int64: cached ones cost nothing, the rest one
+        df pass per MQ_LEX_MAX_TERMS."""
+        miss = [int(x) for x in keys if int(x) not in self.df]
+        tokens, offs = self._views()
+        for at in range(0, len(miss), _lib.MQ_LEX_MAX_TERMS):
+            part = miss[at:at + _lib.MQ_LEX_MAX_TERMS]
+            got = lex_df(tokens, offs, self.ngram, np.array(part, np.uint32), scratch=self.scratch)
+            self.df.update(zip(part, got.tolist()))
+        return np.array([self.df[int(x)] for x in keys], dtype=np.int64)
+
+    def plan(self, query, k1, b):
+        """-> (keys, w, c0, c1) of mq_lex_topk for one query text, or None: no term, or no row
+        has any (avgdl = 0)."""
+        flat, _ = body_tokens(self.tokenizer, [query])
+        terms = term_keys(flat, self.ngram)
+        if not terms.size or self.sum_dl == 0:
+            return None
+        keys, qf = np.unique(terms, return_counts=True)
+        return bm25_plan(keys, qf, self.frequencies(keys), self.n, self.sum_dl / self.n, k1, b)
+
+    def topk(self, plan, k, bits):
+        """-> (scores f32 [k], rows int64 [k]) on the host."""
+        tokens, offs = self._views()
+        keys, w, c0, c1 = plan
+        s, i = lex_topk(tokens, offs, self.ngram, keys, w, c0, c1, k, bits=bits, scratch=self.scratch)
+        return s.cpu().numpy(), i.cpu().numpy()
+
+
+class _LexicalRetriever:
+    """What `HipChroma.as_retriever(search_type="lexical" | "hybrid")` returns: `invoke` /
+    `get_relevant_documents` call the store's method with the retriever's search_kwargs."""
+
+    def __init__(self, store, search_type, search_kwargs):
+        self.vectorstore = store
+        self.search_type = search_type
+        self.search_kwargs = dict(search_kwargs or {})
+
+    def invoke(self, query, config=None, **kwargs):
+        fn = (self.vectorstore.lexical_search if self.search_type == "lexical"
+              else self.vectorstore.hybrid_search)
+        return fn(query, **self.search_kwargs)
+
+    get_relevant_documents = invoke
+
+
 class _IdRows:
     """id -> current row in O(1), kept across deletes without rebuilding a dict of every id:
     each id gets a stable slot when it is added (`slot`, a dict), and two int64 arrays map
@@ -463,9 +644,21 @@ class HipChroma(VectorStoreBase):
     def __init__(self, collection_name="langchain", embedding_function=None,
                  persist_directory=None, client_settings=None, collection_metadata=None,
                  client=None, relevance_score_fn=None, *, device=0, dim=None,
-                 auto_persist=True, search_precision="screen", _ingest=False, **kwargs):
+                 auto_persist=True, search_precision="screen", lexical_tokenizer=None, lexical_ngram=1,
+                 bm25_k1=1.2, bm25_b=0.75, _ingest=False, **kwargs):
         """auto_persist=False: writes stay in memory until `persist()` (bulk ingest);
-        search_precision: SEARCH_PRECISIONS (default "screen": exact fp32 top-k)."""
+        search_precision: SEARCH_PRECISIONS (default "screen": exact fp32 top-k);
+        lexical_tokenizer: the tokenizer of `lexical_search` / `hybrid_search` (default: the
+        embedding function's `tokenizer`), lexical_ngram 1 or 2, bm25_k1 / bm25_b the BM25
+        parameters (include/mq.h)."""
+        if lexical_ngram not in (1, 2):
+            raise ValueError("lexical_ngram must be 1 or 2, got %r" % (lexical_ngram,))
+        if not (math.isfinite(bm25_k1) and bm25_k1 >= 0 and math.isfinite(bm25_b) and 0 <= bm25_b <= 1):
+            raise ValueError("bm25_k1 must be finite and >= 0 and bm25_b in [0, 1], got %r, %r" % (bm25_k1, bm25_b))
+        self._lex_tokenizer = lexical_tokenizer
+        self._lex_ngram = int(lexical_ngram)
+        self._bm25 = (float(bm25_k1), float(bm25_b))
+        self._lex_mirror = None        # _TokenMirror, built at the first lexical use
         if search_precision not in SEARCH_PRECISIONS:
             raise ValueError("search_precision must be one of %s, got %r"
                              % (sorted(SEARCH_PRECISIONS), search_precision))
@@ -928,6 +1121,133 @@ class HipChroma(VectorStoreBase):
             q = np.asarray(self._embedding_function.embed_documents(list(queries)), np.float32)
         return [[self._doc(r) for r in rows]
                 for rows in self._mmr_rows(q, k, fetch_k, lambda_mult, filter, where_document)]
+
+    # ---- lexical (BM25) and hybrid (reciprocal rank fusion) retrieval ----------------------
+    def _lex_tok(self):
+        tok = self._lex_tokenizer
+        if tok is None:
+            tok = getattr(self._embedding_function, "tokenizer", None)
+        if tok is None:
+            raise ValueError("lexical search needs a tokenizer: pass HipChroma(lexical_tokenizer=) or an "
+                             "embedding_function with a `tokenizer`")
+        vocab = getattr(tok, "vocab_size", None)
+        if isinstance(vocab, int) and vocab > 65536:
+            raise ValueError("lexical search stores token ids as uint16: the tokenizer's vocabulary must not "
+                             "exceed 65536 ids (got %d)" % vocab)
+        return tok
+
+    def _lex(self):
+        """The token mirror in step with the store: built at the first use, extended after plain
+        appends (df cache dropped), rebuilt when a delete renumbered the rows."""
+        tok = self._lex_tok()
+        mir = self._lex_mirror
+        if mir is None or mir.epoch != self._text_epoch or mir.tokenizer is not tok:
+            self._lex_mirror = None  # release the old mirror before building the new one
+            mir = self._lex_mirror = _TokenMirror(self._device, self._text_epoch, tok, self._lex_ngram)
+        if mir.version != self._version:
+            mir.extend(self._texts[mir.n:])
+            mir.version = self._version
+        return mir
+
+    def _candidates(self, k, filter, where_document):
+        """-> (k, bits) for a top-k over the store's rows or the rows `filter` / `where_document`
+        admit (bits None: all rows), k clipped as every search here clips it; k = 0: nothing."""
+        n = 0 if self._index is None else len(self._index)
+        if n == 0 or k <= 0:
+            return 0, None
+        if filter or where_document is not None:
+            k, bits = self._admit(k, filter, where_document)
+            return min(int(k), n), bits
+        return _check_k(k, n), None
+
+    def _lex_rows(self, mir, query, k, bits):
+        """-> [(row, bm25 score)] of one query, best first (k already clipped)."""
+        plan = mir.plan(query, *self._bm25) if k > 0 else None
+        if plan is None:
+            return []
+        s, i = mir.topk(plan, int(k), bits)
+        return [(int(r), float(x)) for r, x in zip(i, s) if r >= 0]
+
+    def lexical_search_with_score(self, query, k=DEFAULT_K, filter=None, where_document=None, **kwargs):
+        """(Document, BM25 score) pairs, best first: the rows holding at least one of the query's
+        terms, ranked on the device over the token mirror (include/mq.h, "Lexical retrieval")."""
+        return self.lexical_search_batch_with_score([query], k, filter, where_document)[0]
+
+    def lexical_search(self, query, k=DEFAULT_K, filter=None, where_document=None, **kwargs):
+        return [d for d, _ in self.lexical_search_with_score(query, k, filter, where_document)]
+
+    def lexical_search_batch_with_score(self, queries, k=DEFAULT_K, filter=None, where_document=None):
+        if where_document is not None:
+            _check_where_document(where_document)
+        self._lex_tok()
+        queries = list(queries)
+        k, bits = self._candidates(k, filter, where_document)
+        if k == 0 or not queries:
+            return [[] for _ in queries]
+        mir = self._lex()
+        return [[(self._doc(r), x) for r, x in self._lex_rows(mir, q, k, bits)] for q in queries]
+
+    def lexical_search_batch(self, queries, k=DEFAULT_K, filter=None, where_document=None):
+        """Many queries: the mask is built once, the scans are looped (one launch a query)."""
+        return [[d for d, _ in hits]
+                for hits in self.lexical_search_batch_with_score(queries, k, filter, where_document)]
+
+    def _hybrid(self, queries, k, fetch_k, weights, c, filter, where_document):
+        if where_document is not None:
+            _check_where_document(where_document)
+        _check_rrf(weights, c)
+        self._lex_tok()
+        queries = list(queries)
+        if self._embedding_function is None:
+            raise ValueError("HipChroma needs an embedding_function to search by text")
+        # fetch_k is clipped to MQ_MAX_K and to the candidate rows (fetch_k <= 0: nothing, as MMR's);
+        # k follows the rule of every search here: past MQ_MAX_K it raises unless no more than
+        # MQ_MAX_K rows are candidates
+        fk, bits = self._candidates(min(int(fetch_k), _lib.MQ_MAX_K), filter, where_document)
+        if fk == 0 or k <= 0 or not queries:
+            return [[] for _ in queries]
+        if k > _lib.MQ_MAX_K:
+            k, _ = self._candidates(k, filter, where_document)
+        if len(queries) == 1:
+            q = self._embed_query(queries[0]).reshape(1, -1)
+        elif hasattr(self._embedding_function, "embed_array"):
+            q = self._embedding_function.embed_array(queries)
+        else:
+            q = np.asarray(self._embedding_function.embed_documents(queries), np.float32)
+        q = np.ascontiguousarray(q, dtype=np.float32)
+        _, dense = self._index.search(q, fk) if bits is None else self._index.search_masked(q, fk, bits)
+        mir = self._lex()
+        out = []
+        for query, drow in zip(queries, dense):
+            lex = [r for r, _ in self._lex_rows(mir, query, fk, bits)]
+            fused = rrf_fuse([int(r) for r in drow if r >= 0], lex, weights, c, k)
+            out.append([(self._doc(r), x) for r, x in fused])
+        return out
+
+    def hybrid_search_with_score(self, query, k=DEFAULT_K, fetch_k=20, weights=(0.5, 0.5), c=60, filter=None,
+                                 where_document=None, **kwargs):
+        """(Document, rrf) pairs: the dense top fetch_k (the store's own search) and the lexical
+        top fetch_k fused by weighted reciprocal rank (`rrf_fuse`: LangChain's EnsembleRetriever
+        over [dense, BM25]), the first k.  fetch_k is clipped to the candidate rows and to
+        MQ_MAX_K."""
+        return self._hybrid([query], k, fetch_k, weights, c, filter, where_document)[0]
+
+    def hybrid_search(self, query, k=DEFAULT_K, fetch_k=20, weights=(0.5, 0.5), c=60, filter=None,
+                      where_document=None, **kwargs):
+        return [d for d, _ in self.hybrid_search_with_score(query, k, fetch_k, weights, c, filter, where_document)]
+
+    def hybrid_search_batch(self, queries, k=DEFAULT_K, fetch_k=20, weights=(0.5, 0.5), c=60, filter=None,
+                            where_document=None):
+        """Many queries: one encoder batch, one dense search, looped lexical scans."""
+        return [[d for d, _ in hits]
+                for hits in self._hybrid(queries, k, fetch_k, weights, c, filter, where_document)]
+
+    def as_retriever(self, **kwargs):
+        """search_type "lexical" / "hybrid": a retriever over `lexical_search` / `hybrid_search`
+        with search_kwargs passed on; every other type is the base class's."""
+        if kwargs.get("search_type") in ("lexical", "hybrid"):
+            return _LexicalRetriever(self, kwargs["search_type"], kwargs.get("search_kwargs"))
+        return super().as_retriever(**kwargs)
 
     def _select_relevance_score_fn(self):
         if self.override_relevance_score_fn:
