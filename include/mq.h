@@ -456,6 +456,13 @@ int mq_encoder_set_graphs(mq_encoder* enc, int enabled);
  *                                rounding.  With x6_presplit 0 the same attention follows the QKV
  *                                launch as a launch of its own: the same bits as x6_presplit 1.
  *                                Every other shape runs as with 0, bit for bit.
+ *   MQ_ENC_OPT_EPI_SPLIT         split-f32 precision, x6_presplit 1, the GELU GEMMs (FFN-up, folded
+ *                                or not) on the 128 x 192 / 256 x 96 loader-wave tiles: 1 (default)
+ *                                = at each tile end a compute wave hands two of its four 16-row
+ *                                blocks to the loader wave of its SIMD through the ring slot
+ *                                that is free there, and both finish their rows at the same time;
+ *                                0 = the compute wave finishes the whole wave tile.  The same
+ *                                function on the same values: the same bits either way.
  * Setting an option drops the handle's captured graphs. */
 #define MQ_ENC_OPT_ROWS_MAX 0
 #define MQ_ENC_OPT_ROWS_SPLITS 1
@@ -471,6 +478,7 @@ int mq_encoder_set_graphs(mq_encoder* enc, int enabled);
 #define MQ_ENC_OPT_LN_FOLD 11
 #define MQ_ENC_OPT_CLS_KFREE 12
 #define MQ_ENC_OPT_QKV_ATTN 13
+#define MQ_ENC_OPT_EPI_SPLIT 14
 int mq_encoder_set_option(mq_encoder* enc, int option, int value);
 int mq_encoder_get_option(const mq_encoder* enc, int option, int* value);
 int mq_encoder_set_timing(mq_encoder* enc, int enabled);
@@ -564,12 +572,17 @@ int mq_debug_split_w3(const float* W, int N, int K, void* w3, void* stream);
  * Bit-identical to the split-f32 tiles 5-7 / 9 of mq_debug_gemm_f32 (both on the 16x16x32
  * bf16 MFMA).  16 / 17 = tiles 0 / 7 on the former 32x32x16 k-step, kept for measurement:
  * the same products with 16 k summed per MFMA, fp32-class but not bit-identical.
+ * 20 / 21 = tiles 0 / 1 with the former epilogue, kept for measurement: epi 1 / 2 (GELU) finish
+ * the whole wave tile on its compute wave instead of sharing it with the loader wave
+ * (MQ_ENC_OPT_EPI_SPLIT); bit-identical.  epi 0 / 3 have one form and run as tiles 0 / 1.
  * Asynchronous on `stream`.  K % 32 == 0. */
 int mq_debug_gemm_x6p(const float* A, const void* W3, const float* bias, const float* resid,
                       float* out, int M, int N, int K, int epi, int tile, void* stream);
 /* One K2p launch with a LayerNorm-fold epilogue (tile 0, 1 or -1 = the pick; 20 / 21 = tiles
- * 0 / 1 with the producer's former epilogue - its own residual loads on every tile, no
- * loader-wave hand-off - bit-identical, kept for measurement; no fill-the-chip gate).
+ * 0 / 1 with the former epilogues - the producer's own residual loads on every tile, no
+ * loader-wave hand-off; the GELU consumers' whole wave tile on its compute wave, no split
+ * (MQ_ENC_OPT_EPI_SPLIT); epi 6 has one form - bit-identical, kept for measurement; no
+ * fill-the-chip gate).
  * epi 5 = the producer: out = acc + bias + LN(resid) with the residual normalised from
  * stats_in [M][8] (mean, M2) pairs and g / b [N] (stats_in NULL: the residual as it is), and
  * the partials of out written to stats_out [M][8]; N = 768.  epi 6 / 7 / 8 = the consumers

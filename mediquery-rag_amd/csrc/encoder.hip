@@ -2052,6 +2052,7 @@ struct GemmArgs {
   int nt = 0;  // few-row split-K launches: weights load non-temporally (layers past resident_layers)
   const void* W3 = nullptr;  // split-f32: W's W3 plane image (K2p, gemm_x6p.hip)
   LnFold lf{};               // the LayerNorm-fold epilogues (launch_gemm_fold)
+  bool former_epi = false;   // K2p: the single-wave GELU epilogue (MQ_ENC_OPT_EPI_SPLIT 0)
 };
 
 template <class T, int EPI, bool LN_IN = false>
@@ -2166,6 +2167,7 @@ void launch_gemm_fold(const GemmArgs& g, int num_cus, hipStream_t s) {
   if (g.W3) {
     X6pArgs a{g.A, g.lda, g.W3, g.bias, g.resid, g.ldr, g.out, g.ldo, g.M, g.N, g.K};
     a.lf = g.lf;
+    a.former_epi = g.former_epi;
     launch_gemm_x6p(a, EPI, -1, num_cus, s);
     return;
   }
@@ -2194,8 +2196,9 @@ void launch_gemm(const GemmArgs& g, int num_cus, hipStream_t s, bool x6 = false,
   // 3.09-3.16 ms p50 on either split-f32 path, 2.45 on exact f32)
   if (x6 && (int64_t)((g.M + 127) / 128) * ((g.N + 191) / 192) < num_cus) x6 = false;
   if (x6 && g.W3) {  // split-f32 on the pre-split weights (K2p)
-    launch_gemm_x6p(X6pArgs{g.A, g.lda, g.W3, g.bias, g.resid, g.ldr, g.out, g.ldo, g.M, g.N, g.K}, EPI, -1, num_cus,
-                    s);
+    X6pArgs a{g.A, g.lda, g.W3, g.bias, g.resid, g.ldr, g.out, g.ldo, g.M, g.N, g.K};
+    a.former_epi = g.former_epi;
+    launch_gemm_x6p(a, EPI, -1, num_cus, s);
     return;
   }
   if (x6) {  // split-f32 tiles (both operands split while staged): same waste model over 128x{128,96,64}
@@ -2257,6 +2260,11 @@ constexpr bool kClsKfreeDefault = MQ_CLS_KFREE_DEFAULT != 0;
 #define MQ_QKV_ATTN_DEFAULT 1
 #endif
 constexpr bool kQkvAttnDefault = MQ_QKV_ATTN_DEFAULT != 0;
+// MQ_ENC_OPT_EPI_SPLIT's default (DESIGN.md section 4 has the A/B that decides it)
+#ifndef MQ_EPI_SPLIT_DEFAULT
+#define MQ_EPI_SPLIT_DEFAULT 1
+#endif
+constexpr bool kEpiSplitDefault = MQ_EPI_SPLIT_DEFAULT != 0;
 
 // Stage labels for the optional per-kernel-class event timeline.
 enum Stage { ST_EMBED = 0, ST_QKV, ST_ATTN, ST_OPROJ, ST_LN, ST_FFN_UP, ST_FFN_DOWN, ST_POOL, ST_N };
@@ -2311,6 +2319,7 @@ struct mq_encoder {
   bool rows_planes = false;     // few-row forward: keep the two-plane hand-offs (no FL_ACC merge)
   bool cls_kfree = kClsKfreeDefault;  // CLS pooling, batched forward: the last layer without K / V
   bool qkv_attn = kQkvAttnDefault;    // split-f32 batched forward, L = 32: attention in the QKV epilogue
+  bool epi_split = kEpiSplitDefault;  // K2p's GELU epilogues shared out between both waves of each SIMD
   Buf wkt;                      // its Wk^T of the last layer [H][H], built at weight load
   Buf cls;                      // its [B] rows: normalised CLS rows, q (H each), u, z (heads H each), live
   // cross-encoder head (mq_encoder_load_head): Wp [H][H], bp [H], Wc [n_labels][H], bc [n_labels]
@@ -2464,6 +2473,7 @@ void gemm(mq_encoder* e, const GemmArgs& g, int stage, hipStream_t s) {
   e->tl.mark(s, stage);
   GemmArgs a = g;
   if (!e->x6_presplit) a.W3 = nullptr;
+  a.former_epi = !e->epi_split;
   launch_gemm<EPI>(a, e->num_cus, s, e->precision == MQ_DTYPE_F32X6, e->splitk_max, e->splitk_tiles);
 }
 
@@ -2637,6 +2647,7 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* types, const int* mask
   auto fold_gemm = [&](auto epi, GemmArgs g, int stage) {
     e->tl.mark(s, stage);
     if (!e->x6_presplit) g.W3 = nullptr;
+    g.former_epi = !e->epi_split;
     g.lf.eps = c.ln_eps;
     launch_gemm_fold<decltype(epi)::value>(g, e->num_cus, s);
   };
@@ -3694,6 +3705,10 @@ int mq_encoder_set_option(mq_encoder* e, int option, int value) {
       MQ_CHECK_ARG(value == 0 || value == 1, "qkv_attn must be 0 or 1 (got %d)", value);
       e->qkv_attn = value != 0;
       break;
+    case MQ_ENC_OPT_EPI_SPLIT:
+      MQ_CHECK_ARG(value == 0 || value == 1, "epi_split must be 0 or 1 (got %d)", value);
+      e->epi_split = value != 0;
+      break;
     default:
       MQ_FAIL(MQ_EINVAL, "unknown encoder option %d", option);
   }
@@ -3721,6 +3736,7 @@ int mq_encoder_get_option(const mq_encoder* e, int option, int* value) {
     case MQ_ENC_OPT_LN_FOLD: *value = e->ln_fold ? 1 : 0; break;
     case MQ_ENC_OPT_CLS_KFREE: *value = e->cls_kfree ? 1 : 0; break;
     case MQ_ENC_OPT_QKV_ATTN: *value = e->qkv_attn ? 1 : 0; break;
+    case MQ_ENC_OPT_EPI_SPLIT: *value = e->epi_split ? 1 : 0; break;
     default: MQ_FAIL(MQ_EINVAL, "unknown encoder option %d", option);
   }
   return MQ_OK;

@@ -356,11 +356,41 @@ __device__ __forceinline__ void ln_tile_write(const LnTileRegs<MB, NB>& q, unsig
   }
 }
 
+// [M_LO, M_HI): the block rows this call finishes (K2p's split epilogue, gemm_x6p.hip: a wave tile's
+// block rows shared out between two waves; the block rows outside the range are not read).  Which
+// path a wave tile takes - whole or ragged - is decided on the whole wave tile, and ln_row_own is
+// taken over all MB block rows (lane 4 m + e of a row group holds row e of block row m whatever
+// the range): a block row's values do not depend on the range it is finished in.
+//
+// EpiPre / epi_pre_load: what the bias / GELU / fold kinds read from memory besides the
+// accumulators - the lane's bias (and s) of each block column, columns clamped to N - 1 (a clamped
+// column is never stored), and its row statistics - loaded ahead of time, so that a wave that
+// receives its block rows late (the split epilogue's loader wave) has them when the rows arrive.
+// With `pre` the store reads none of them itself: the same values, so the same bits.
+template <int NB>
+struct EpiPre {
+  float bv[NB], sv[NB];
+  float own_mu = 0.f, own_rho = 0.f;
+};
 template <int EPI, int MB, int NB>
+__device__ __forceinline__ void epi_pre_load(EpiPre<NB>& p, int wr0, int wc0, int M, int N,
+                                             const float* __restrict__ bias, const LnFold& lf, int lane) {
+#pragma unroll
+  for (int n = 0; n < NB; ++n) {
+    const int col = min(wc0 + n * 16 + (lane & 15), N - 1);
+    p.bv[n] = bias[col];
+    p.sv[n] = epi_is_lnfold(EPI) ? lf.s[col] : 0.f;
+  }
+  if constexpr (epi_is_lnfold(EPI)) ln_row_own<MB>(lf.stats_in, wr0, M, lf.eps, lane, p.own_mu, p.own_rho);
+}
+template <int EPI, int MB, int NB, int M_LO = 0, int M_HI = MB, bool PRE = false>
 __device__ __forceinline__ void store_wave_tile16(floatx4 (&acc)[MB][NB], int wr0, int wc0, int M, int N,
                                                   const float* __restrict__ bias, const float* __restrict__ resid,
                                                   int ldr, float* __restrict__ out, int ldo, int lane,
-                                                  const LnFold& lf = LnFold{}) {
+                                                  const LnFold& lf = LnFold{}, const EpiPre<NB>* pre = nullptr) {
+  static_assert(!PRE || (EPI != EPI_RESID && EPI != EPI_RESID_LN_STATS), "preloads: the kinds without a residual");
+  static_assert(0 <= M_LO && M_LO < M_HI && M_HI <= MB, "block-row range");
+  static_assert(EPI != EPI_RESID_LN_STATS || (M_LO == 0 && M_HI == MB), "the producer finishes whole wave tiles");
   const int c = lane & 15, g = lane >> 4;
   if constexpr (EPI == EPI_RESID_LN_STATS) {
     // one row at a time: K2p's default tiles spill 4 VGPRs at two rows, 32 at four (tools/spill_audit.py)
@@ -371,14 +401,29 @@ __device__ __forceinline__ void store_wave_tile16(floatx4 (&acc)[MB][NB], int wr
   constexpr bool FOLD = epi_is_lnfold(EPI);
   static_assert(!FOLD || MB <= 4, "one lane of a 16-lane row group per row of the wave tile");
   float own_mu = 0.f, own_rho = 0.f;  // this lane's row of A (ln_row_own)
-  if constexpr (FOLD) ln_row_own<MB>(lf.stats_in, wr0, M, lf.eps, lane, own_mu, own_rho);
+  if constexpr (PRE) {
+    own_mu = pre->own_mu;
+    own_rho = pre->own_rho;
+  } else if constexpr (FOLD) {
+    ln_row_own<MB>(lf.stats_in, wr0, M, lf.eps, lane, own_mu, own_rho);
+  }
   if (wr0 + MB * 16 <= M && wc0 + NB * 16 <= N) {
     float bv[NB], sv[NB];
 #pragma unroll
-    for (int n = 0; n < NB; ++n) bv[n] = bias[wc0 + n * 16 + c];
+    for (int n = 0; n < NB; ++n) {
+      if constexpr (PRE)
+        bv[n] = pre->bv[n];
+      else
+        bv[n] = bias[wc0 + n * 16 + c];
+    }
     if constexpr (FOLD) {
 #pragma unroll
-      for (int n = 0; n < NB; ++n) sv[n] = lf.s[wc0 + n * 16 + c];
+      for (int n = 0; n < NB; ++n) {
+        if constexpr (PRE)
+          sv[n] = pre->sv[n];
+        else
+          sv[n] = lf.s[wc0 + n * 16 + c];
+      }
     }
     const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(resid + (EPI == EPI_RESID ? (int64_t)wr0 * ldr + wc0 : 0)), (short)0, 0x7fffffff, 0x00020000);
@@ -387,7 +432,7 @@ __device__ __forceinline__ void store_wave_tile16(floatx4 (&acc)[MB][NB], int wr
         (void*)(out + (int64_t)wr0 * ldo + wc0), (short)0, 0x7fffffff, 0x00020000);
     const int ol = (4 * g * ldo + c) * 4;
 #pragma unroll
-    for (int m = 0; m < MB; ++m) {
+    for (int m = M_LO; m < M_HI; ++m) {
       float rv[NB][4];
       if constexpr (EPI == EPI_RESID) {
 #pragma unroll
@@ -422,7 +467,7 @@ __device__ __forceinline__ void store_wave_tile16(floatx4 (&acc)[MB][NB], int wr
   }
   if constexpr (FOLD) {  // ragged edge (the row statistics are shared by shuffle: no lane may have left)
 #pragma unroll
-    for (int m = 0; m < MB; ++m) {
+    for (int m = M_LO; m < M_HI; ++m) {
       float mu[4], rho[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -433,7 +478,14 @@ __device__ __forceinline__ void store_wave_tile16(floatx4 (&acc)[MB][NB], int wr
       for (int n = 0; n < NB; ++n) {
         const int col = wc0 + n * 16 + c;
         if (col < N) {
-          const float b = bias[col], sn = lf.s[col];
+          float b, sn;
+          if constexpr (PRE) {
+            b = pre->bv[n];
+            sn = pre->sv[n];
+          } else {
+            b = bias[col];
+            sn = lf.s[col];
+          }
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const int row = wr0 + m * 16 + 4 * g + e;
@@ -449,9 +501,13 @@ __device__ __forceinline__ void store_wave_tile16(floatx4 (&acc)[MB][NB], int wr
   for (int n = 0; n < NB; ++n) {
     const int col = wc0 + n * 16 + c;
     if (col >= N) continue;
-    const float b = bias[col];
+    float b;
+    if constexpr (PRE)
+      b = pre->bv[n];
+    else
+      b = bias[col];
 #pragma unroll
-    for (int m = 0; m < MB; ++m)
+    for (int m = M_LO; m < M_HI; ++m)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int row = wr0 + m * 16 + 4 * g + e;

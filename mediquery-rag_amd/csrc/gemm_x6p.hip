@@ -156,9 +156,25 @@ struct X6pTile {
   static_assert(AHEAD >= 2 && NBUF * STAGE <= 160 * 1024, "LDS ring");
 };
 
-// FORMER (tile codes 20 / 21 of mq_debug_gemm_x6p_ln): the producer's epilogue as it was before
-// the loader-wave hand-off - its own global loads on every tile - kept to re-measure the two in
-// one library.  Same results, bit for bit.
+// The split epilogue's kinds and the block rows (of a wave tile's 4) a compute wave hands to its
+// SIMD partner (1 or 2; tools/gemm_x6p_bench.py --ab measures a library built with the other).
+// MQ_X6P_SPLIT_BIAS builds the split form of the two bias kinds as well (measured, not shipped:
+// DESIGN.md section 4).
+#ifndef MQ_X6P_HS
+#define MQ_X6P_HS 2
+#endif
+#ifndef MQ_X6P_SPLIT_BIAS
+#define MQ_X6P_SPLIT_BIAS 0
+#endif
+constexpr bool epi_is_split(int epi) {
+  return epi == EPI_GELU_ERF || epi == EPI_GELU_TANH || epi == EPI_GELU_ERF_LNFOLD || epi == EPI_GELU_TANH_LNFOLD ||
+         (MQ_X6P_SPLIT_BIAS != 0 && (epi == EPI_BIAS || epi == EPI_BIAS_LNFOLD));
+}
+
+// FORMER (tile codes 20 / 21 of mq_debug_gemm_x6p and mq_debug_gemm_x6p_ln): the epilogues as
+// they were before the loader waves took part - the producer's own global loads on every tile
+// (no hand-off), the consumers' whole wave tile finished by its compute wave (no split) - kept to
+// re-measure the two in one library.  Same results, bit for bit.
 //
 // The producer's hand-off (HAND: EPI_RESID_LN_STATS on the loader-wave tiles X6p0 / X6p1).  On
 // the workgroup's LAST tile the loader wave prepares its SIMD partner's residual during the
@@ -223,6 +239,36 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
                 "attention epilogue: the 128 x 192 loader-wave tile");
   static_assert(!HAND || (T::NW == 4 && 2 * T::WM * T::WN * 4 <= T::STAGE && T::WN == kLnPartW && T::STAGE % 1024 == 0),
                 "hand-off: two wave tiles of t per ring slot");
+  // SPLIT (the GELU consumer kinds on the loader-wave tiles X6p0 / X6p1): at a tile end the
+  // compute wave hands the last HS of its MB = 4 block rows to its SIMD partner, the loader wave
+  // of the same cw, and both finish their rows with the same store_wave_tile16 at the same time:
+  // two VALU streams per SIMD instead of one (a single wave issues a VALU instruction every 4
+  // cycles at best, the SIMD one every 2).  Nothing overlaps the next tile's k-loop: the two meet
+  // again at the stage barrier they already share.
+  //   Slot plan.  Stage j, a tile's last, sits in slot j % 3.  As for ATTN above, the compute
+  //   waves wait lgkmcnt(0) before B(j + 1), so slot j % 3 is free from B(j + 1) to B(j + 2): the
+  //   loader refills it (stage j + 3) only after B(j + 2), which every wave reaches after its
+  //   part of the epilogue.  Compute wave cw writes its HS x NB16 handed accumulator blocks, 1 KB
+  //   each (one ds_write_b128 per block, lane l at byte 16 l), to slot j % 3 at cw HS NB16 1 KB
+  //   (4 HS 6 KB <= STAGE); the loader wave reads them back lane-identically: the same register
+  //   image, the same function, the same bits.  Slots (j + 1) % 3 and (j + 2) % 3 - stage j + 1,
+  //   whose operands the compute wave keeps in registers across the epilogue, and stage j + 2,
+  //   being filled - are untouched.
+  //   Barriers, per role (every wave of the workgroup executes each exactly once):
+  //                         compute waves                        loader waves
+  //     prologue  B(0)      before reading stage 0               after vmcnt: stage 0 landed
+  //     stage j   B(j + 1)  top of iteration j (tile's last      stage j + 1 landed
+  //                         stage: after lgkmcnt(0))
+  //     tile end  X(j)      after iteration j's MFMAs, handed    after issuing stage j + 2 and the
+  //               (j % nst == nst - 1)  rows written, lgkmcnt(0) loads of bias / s / row statistics
+  //   i.e. S + 1 + n_tiles on both sides; no barrier depends on M, on N or on the path (whole or
+  //   ragged) a wave tile takes.  The loader wave's stores are covered by the vmcnt(0) of its
+  //   next wait_stages (or the one after its loop).
+  constexpr int HS = MQ_X6P_HS;
+  constexpr bool SPLIT = epi_is_split(EPI) && !FORMER && T::LDR && T::M16 && !T::DEEP && T::NBUF == 3 && T::TM == 2 &&
+                         T::TN == 3;
+  static_assert(!SPLIT || ((HS == 1 || HS == 2) && 4 * HS * 2 * T::TN * 1024 <= T::STAGE),
+                "split epilogue: the handed blocks of the four compute waves fit one ring slot");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int cw = T::LDR ? wave % T::NW : wave;  // compute wave index
@@ -514,6 +560,7 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
         return;
       }
       int l_st = 0;
+      [[maybe_unused]] int l_i = 0;
       for (int j = 0; j < S; ++j) {
         wait_stages(IC<T::AHEAD - 2>{});  // stage j + 1 landed
         issue((j + T::AHEAD) % T::NBUF);  // stage j + AHEAD
@@ -521,6 +568,28 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
           if (++l_st == nst) {  // X(j): the compute waves' exchange barrier of this tile end
             l_st = 0;
             asm volatile("s_barrier" ::: "memory");
+          }
+        }
+        if constexpr (SPLIT) {
+          if (++l_st == nst) {  // stage j is a tile's last (the kernel's comment has the plan)
+            l_st = 0;
+            static_assert(T::AHEAD == 2, "split epilogue: the ring two stages ahead");
+            constexpr int MB = 2 * T::TM, NB16 = 2 * T::TN;
+            int m0, n0;
+            coords(l_i++, m0, n0);
+            const int wr0 = m0 + wm * T::WM, wc0 = n0 + wn * T::WN;
+            EpiPre<NB16> pre;  // in flight while the compute waves multiply stage j
+            epi_pre_load<EPI, MB, NB16>(pre, wr0, wc0, M, N, bias, lf, lane);
+            asm volatile("s_barrier" ::: "memory");  // X(j): the handed block rows are in slot j % 3
+            const unsigned char* hs = lds + (j % T::NBUF) * T::STAGE + cw * (HS * NB16 * 1024) + lane * 16;
+            floatx4 hacc[MB][NB16];  // (rows below MB - HS are never read)
+#pragma unroll
+            for (int m = 0; m < HS; ++m)
+#pragma unroll
+              for (int n = 0; n < NB16; ++n)
+                hacc[MB - HS + m][n] = *reinterpret_cast<const floatx4*>(hs + (m * NB16 + n) * 1024);
+            store_wave_tile16<EPI, MB, NB16, MB - HS, MB, true>(hacc, wr0, wc0, M, N, bias, resid, ldr, out, ldo, lane,
+                                                                lf, &pre);
           }
         }
       }
@@ -616,7 +685,7 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
         wait_stages(IC<T::AHEAD - 2>{});
       } else {
         if constexpr (T::DEEP) __builtin_amdgcn_s_waitcnt(0xC07F);
-        if constexpr (ATTN) {  // a tile's last stage: its slot is the epilogue's, no read of it may be in flight
+        if constexpr (ATTN || SPLIT) {  // a tile's last stage: its slot is the epilogue's, no read of it may be in flight
           if (c_st == nst - 1) __builtin_amdgcn_s_waitcnt(0xC07F);
         }
         asm volatile("s_barrier" ::: "memory");
@@ -662,6 +731,20 @@ __global__ __launch_bounds__(T::THREADS, 1) void gemm_x6p_kernel(const float* __
           // stage j + 1 again: its prefetched copies died above.  Unconditional, so that no path
           // carries them across the epilogue (after the last tile the values are never used)
           load_ops(st);
+        } else if constexpr (SPLIT) {
+          // the last HS block rows to the SIMD partner, through stage j's slot (free until B(j + 2))
+          unsigned char* hs = lds + (j % T::NBUF) * T::STAGE + cw * (HS * NB16 * 1024) + lane * 16;
+#pragma unroll
+          for (int m = 0; m < HS; ++m)
+#pragma unroll
+            for (int n = 0; n < NB16; ++n)
+              *reinterpret_cast<floatx4*>(hs + (m * NB16 + n) * 1024) = acc4[MB - HS + m][n];
+          __builtin_amdgcn_s_waitcnt(0xC07F);       // they are in LDS
+          asm volatile("s_barrier" ::: "memory");  // X(j)
+          // (its own loads stay behind the barrier: issued in front of it, the row statistics' 16 load
+          // registers beside the accumulators and the next stage's operands spill 7 - 9 VGPRs)
+          store_wave_tile16<EPI, MB, NB16, 0, MB - HS>(acc4, m0 + wm * T::WM, n0 + wn * T::WN, M, N, bias, resid, ldr,
+                                                       out, ldo, lane, lf);
         } else {
           store_wave_tile16<EPI, MB, NB16>(acc4, m0 + wm * T::WM, n0 + wn * T::WN, M, N, bias, resid, ldr, out, ldo,
                                            lane, lf);
@@ -871,15 +954,18 @@ void launch_tile(const X6pArgs& g, int tile, int num_cus, hipStream_t s) {
     case 7: launch_t<X6p7, EPI>(g, num_cus, s); return;
     case 16: launch_t<X6p16, EPI>(g, num_cus, s); return;
     case 17: launch_t<X6p17, EPI>(g, num_cus, s); return;
+    // 20 / 21: tiles 0 / 1 with the former epilogue (kinds that have one form run as 0 / 1)
+    case 20: launch_t<X6p0, EPI, epi_is_split(EPI)>(g, num_cus, s); return;
+    case 21: launch_t<X6p1, EPI, epi_is_split(EPI)>(g, num_cus, s); return;
     default: launch_t<X6p0, EPI>(g, num_cus, s); return;
   }
 }
 
-// the LayerNorm-fold epilogues: the default tiles only; 20 / 21 = tiles 0 / 1 with the producer's
-// former epilogue (no hand-off; the consumers have one form)
+// the LayerNorm-fold epilogues: the default tiles only; 20 / 21 = tiles 0 / 1 with the former
+// epilogue (the producer without its hand-off, the GELU consumers without the split)
 template <int EPI>
 void launch_tile_fold(const X6pArgs& g, int tile, int num_cus, hipStream_t s) {
-  constexpr bool HAS_FORMER = EPI == EPI_RESID_LN_STATS;
+  constexpr bool HAS_FORMER = EPI == EPI_RESID_LN_STATS || epi_is_split(EPI);
   switch (tile) {
     case 1: launch_t<X6p1, EPI>(g, num_cus, s); return;
     case 20: launch_t<X6p0, EPI, HAS_FORMER>(g, num_cus, s); return;
@@ -954,6 +1040,8 @@ void launch_gemm_x6p(const X6pArgs& g, int epi, int tile, int num_cus, hipStream
     // profiles/mfma16/gemm_ab.jsonl)
     tile = x6p_pick_tile(g.M, g.N, num_cus);
   }
+  // MQ_ENC_OPT_EPI_SPLIT 0: the single-wave consumer epilogue (the producer keeps its hand-off)
+  if (g.former_epi && epi_is_split(epi) && (tile == 0 || tile == 1)) tile += 20;
   switch (epi) {
     case EPI_GELU_ERF: launch_tile<EPI_GELU_ERF>(g, tile, num_cus, s); return;
     case EPI_GELU_TANH: launch_tile<EPI_GELU_TANH>(g, tile, num_cus, s); return;
@@ -995,7 +1083,8 @@ int mq_debug_gemm_x6p(const float* A, const void* W3, const float* bias, const f
   // plain walk); below 100 the automatic pick
   const int rx = tile >= 100 ? tile / 100 - 1 : -1;
   if (tile >= 100) tile %= 100;
-  MQ_CHECK_ARG(epi >= 0 && epi <= 3 && tile >= -1 && tile <= 17 && rx <= 8, "bad epi/tile");
+  MQ_CHECK_ARG(epi >= 0 && epi <= 3 && tile >= -1 && (tile <= 17 || tile == 20 || tile == 21) && rx <= 8,
+               "bad epi/tile");
   int dev = 0, cus = 256;
   (void)hipGetDevice(&dev);
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);

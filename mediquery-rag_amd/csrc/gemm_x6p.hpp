@@ -119,6 +119,9 @@ struct X6pArgs {
   // H = 64 heads, M a multiple of 32, `out` is ctx [M][ldo], mask [M] int32, scale on Q
   AttnEpi at{};
   int max_wg = 0;  // > 0 (a multiple of 8): at most this many workgroups (tests: long tile walks)
+  // tiles 0 / 1, the GELU kinds: the whole wave tile finished by its compute wave, as tile codes
+  // 20 / 21 (MQ_ENC_OPT_EPI_SPLIT 0); the same bits
+  bool former_epi = false;
 };
 
 // The attention of EPI_ATTN_* as a launch of its own, from a qkv [M][3 H] buffer that an unfused
@@ -132,7 +135,8 @@ void launch_attn32(const float* qkv, const int* mask, float* ctx, int M, int H, 
 // tiles), 1 = 256 x 96 (same waves), 2 = 128 x 192 and 3 = 256 x 192 (8 compute waves),
 // 7 = 64 x 192 (4 + 4 waves); 4-6 are tiles 0 / 7 / 1 with the ring one stage further
 // ahead (measurement); 16 / 17 are tiles 0 / 7 on the former 32x32x16 k-step (measurement;
-// fp32-class, not bit-identical to the others).  -1 = the pick below.
+// fp32-class, not bit-identical to the others); 20 / 21 are tiles 0 / 1 with the former epilogues
+// (measurement; bit-identical).  -1 = the pick below.
 int x6p_pick_tile(int M, int N, int num_cus);
 // epi: EPI_BIAS / EPI_GELU_ERF / EPI_GELU_TANH / EPI_RESID (gemm_epi.hpp); the LayerNorm-fold
 // kinds (g.lf) on tiles 0 and 1 only, K % 32 == 0

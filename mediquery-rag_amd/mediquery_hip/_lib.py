@@ -35,6 +35,7 @@ MQ_ENC_OPT_ROWS_PLANES = 10
 MQ_ENC_OPT_LN_FOLD = 11
 MQ_ENC_OPT_CLS_KFREE = 12
 MQ_ENC_OPT_QKV_ATTN = 13
+MQ_ENC_OPT_EPI_SPLIT = 14
 MQ_ROWS_QKV, MQ_ROWS_UP, MQ_ROWS_OPROJ, MQ_ROWS_DOWN = 0, 1, 2, 3  # mq_debug_rows_gemm kinds
 
 

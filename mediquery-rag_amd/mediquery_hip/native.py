@@ -309,7 +309,8 @@ class Encoder:
                "splitk_tiles": _lib.MQ_ENC_OPT_SPLITK_TILES, "ln_on_load": _lib.MQ_ENC_OPT_LN_ON_LOAD,
                "resident_layers": _lib.MQ_ENC_OPT_RESIDENT_LAYERS, "x6_presplit": _lib.MQ_ENC_OPT_X6_PRESPLIT,
                "rows_planes": _lib.MQ_ENC_OPT_ROWS_PLANES, "ln_fold": _lib.MQ_ENC_OPT_LN_FOLD,
-               "cls_kfree": _lib.MQ_ENC_OPT_CLS_KFREE, "qkv_attn": _lib.MQ_ENC_OPT_QKV_ATTN}
+               "cls_kfree": _lib.MQ_ENC_OPT_CLS_KFREE, "qkv_attn": _lib.MQ_ENC_OPT_QKV_ATTN,
+               "epi_split": _lib.MQ_ENC_OPT_EPI_SPLIT}
 
     def set_option(self, name, value):
         """Tuning option of the forward (mq_encoder_set_option): rows_max, rows_splits,
@@ -324,7 +325,10 @@ class Encoder:
         1, default, the last layer attends from the CLS query without projecting K and V; 0 =
         the all-token K / V projection and the attention kernel; equal to rounding), qkv_attn
         (split-f32 precision, batched forward, L == 32: 1, default, the attention runs in the
-        QKV GEMM's epilogue; 0 = the QKV launch and the attention launch; equal to rounding)."""
+        QKV GEMM's epilogue; 0 = the QKV launch and the attention launch; equal to rounding),
+        epi_split (split-f32 precision, x6_presplit 1: 1, default, shares each GELU tile
+        epilogue of the loader-wave split-f32 tiles between the compute wave and the loader wave of
+        its SIMD; 0 = the compute wave alone; bit-identical)."""
         _lib.call("mq_encoder_set_option", self._h, self.OPTIONS[name], int(value))
 
     def get_option(self, name):

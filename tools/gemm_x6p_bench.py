@@ -46,12 +46,16 @@ def ab(a, dev, st):
     LayerNorm-fold epilogues (mq_debug_gemm_x6p_ln: the producer, epi 5 with stats_in, for the
     residual shapes, the consumers 6 / 7 / 8 for the others), e.g. --ab 20:0 for the producer's
     former epilogue against the loader-wave hand-off on tile 0.  Codes 20 / 21 differ from 0 / 1
-    on the producer shapes (out_proj, ffn_down) only: a pair that names them skips the others
-    (it would time one kernel twice)."""
+    on the producer shapes (out_proj, ffn_down; --ln-fold only) and on the GELU kinds (ffn_up, or
+    --epi 1 / 2: the split epilogue, with and without --ln-fold): a pair that names them skips the
+    others (it would time one kernel twice).  --epi overrides the kind of the non-residual
+    shapes (0 bias, 1 GELU erf, 2 GELU tanh; with --ln-fold 6 / 7 / 8)."""
     pairs = [tuple(int(t) for t in p.split(":")) for p in a.ab.split(",")]
     out_f = open(a.out, "a") if a.out else None
     for name in a.shapes.split(","):
         M, N, K, epi = SHAPES[name]
+        if a.epi >= 0 and epi != 3:
+            epi = a.epi
         g = torch.Generator(device=dev).manual_seed(1)
         A = torch.randn(M, K, device=dev, generator=g)
         W = torch.randn(N, K, device=dev, generator=g) * 0.05
@@ -62,7 +66,8 @@ def ab(a, dev, st):
         _lib.call("mq_debug_split_w3", _lib.ptr(W), N, K, _lib.ptr(w3), st)
         ref = A.double() @ W.double().T + b.double() if a.check else None
         fepi = 5 if epi == 3 else 6 + epi
-        if a.ln_fold and fepi != 5:
+        has_former = epi in (1, 2) and not a.check or (a.ln_fold and fepi == 5) or a.split_bias
+        if not has_former:
             pairs_here = [p for p in pairs if not {20, 21} & set(p)]
         else:
             pairs_here = pairs
@@ -247,6 +252,11 @@ def main():
     ap.add_argument("--ab", default="", help="OLD:NEW tile code pairs to time alternating (see ab())")
     ap.add_argument("--out", default="", help="--ab / --attn: also append the JSON lines to this file")
     ap.add_argument("--check", action="store_true", help="--ab: bias epilogue, report max |err| vs float64")
+    ap.add_argument("--epi", type=int, default=-1, choices=[-1, 0, 1, 2],
+                    help="--ab: the kind of the non-residual shapes (default: the shape's own)")
+    ap.add_argument("--split-bias", action="store_true",
+                    help="--ab: the library was built with -DMQ_X6P_SPLIT_BIAS=1, so 20 / 21 differ on the bias "
+                         "kinds too")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--f32-tiles", default="0,1,5,6,7")
