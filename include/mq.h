@@ -397,22 +397,11 @@ int mq_encoder_set_graphs(mq_encoder* enc, int enabled);
  *                                it divides ffn / 256 into an instantiated depth)
  *   MQ_ENC_OPT_SPLITK_MAX        deepest split-K of the tiled path's few-row GEMMs (2..64,
  *                                default 16)
- *   MQ_ENC_OPT_LN_ROWS_PER_WAVE  rows per wave of the batched LayerNorm kernel (1, 2, 4;
- *                                default 4)
  *   MQ_ENC_OPT_FUSE_ATTN_OPROJ   few-row forward: attention + output projection in one
  *                                launch (1, default) or two (0)
- *   MQ_ENC_OPT_FUSED_LN          batched forward, exact f32, hidden <= 768: the residual
- *                                projections (out-proj, FFN-down) on full-row tiles with
- *                                the LayerNorm in their epilogue (1) or GEMM + LayerNorm
- *                                launch (0, default: the full-row tiles measured slower)
  *   MQ_ENC_OPT_SPLITK_TILES      tiled path, M <= 256 rows: a GEMM is split over K only when
  *                                its direct grid has at most this many 32 x 128 tiles
  *                                (0..4096, default 0 = one tile per CU)
- *   MQ_ENC_OPT_LN_ON_LOAD        batched forward, exact f32, M > 256, hidden 768: the
- *                                LayerNorms applied by the consuming GEMM while it stages its
- *                                input, from per-row partials the residual GEMM leaves (1), or
- *                                a LayerNorm launch each (0, default: the staging VALU cost the
- *                                QKV / FFN-up GEMMs 16-18%, more than the 24 launches save)
  *   MQ_ENC_OPT_RESIDENT_LAYERS   few-row forward: layers [0, value) load their weights with
  *                                the default cache policy, later layers non-temporally, so
  *                                back-to-back single queries keep the first layers' weights
@@ -463,15 +452,13 @@ int mq_encoder_set_graphs(mq_encoder* enc, int enabled);
  *                                that is free there, and both finish their rows at the same time;
  *                                0 = the compute wave finishes the whole wave tile.  The same
  *                                function on the same values: the same bits either way.
- * Setting an option drops the handle's captured graphs. */
+ * Setting an option drops the handle's captured graphs.
+ * (Ids 3, 5 and 7: retired, never reuse.) */
 #define MQ_ENC_OPT_ROWS_MAX 0
 #define MQ_ENC_OPT_ROWS_SPLITS 1
 #define MQ_ENC_OPT_SPLITK_MAX 2
-#define MQ_ENC_OPT_LN_ROWS_PER_WAVE 3
 #define MQ_ENC_OPT_FUSE_ATTN_OPROJ 4
-#define MQ_ENC_OPT_FUSED_LN 5
 #define MQ_ENC_OPT_SPLITK_TILES 6
-#define MQ_ENC_OPT_LN_ON_LOAD 7
 #define MQ_ENC_OPT_RESIDENT_LAYERS 8
 #define MQ_ENC_OPT_X6_PRESPLIT 9
 #define MQ_ENC_OPT_ROWS_PLANES 10

@@ -32,29 +32,6 @@
 
 namespace mq {
 
-
-// LayerNorm deferred into the consumer (batched path, MQ_ENC_OPT_LN_ON_LOAD).  The
-// residual GEMM (out-proj / FFN-down, EPI_RESID_STATS) writes y = A W^T + b + resid and,
-// per row and per wave tile of kLnPartW columns, the partial (mean, M2) of y: stats[row][t].
-// The next GEMM (FFN-up / the next layer's QKV, LN_IN) merges a row's partials into (mean,
-// rstd) once per tile (Chan: M2 = sum M2_t + w sum (mean_t - mean)^2, equal counts w) and
-// normalises every A element between its global load and its LDS write, (y - mean) rstd
-// gamma + beta; the tiles of column 0 also store LN(y) to x, the residual input of the
-// following residual GEMM.  No LayerNorm launch and no y -> x round trip.  Two-pass-class
-// statistics in fp32; ln_kernel's summation order differs (results agree to rounding).
-// (kLnPartW = 96 columns per partial, the producer's wave tile F32Tile<4,1,1,3>, and
-// kLnMaxParts = 8 partials per row - the path runs at H = 768 - are gemm_x6p.hpp's.)
-struct LnArgs {
-  float* stats_out;       // producer: [M][nt] (mean, M2) pairs
-  const float* stats_in;  // consumer: the producer's pairs for A's rows
-  const float* g;         // consumer: LayerNorm gamma [K]
-  const float* b;         //           beta [K]
-  float* xout;            //           column-0 tiles store LN(A) rows here
-  int ldx;
-  int nt;                 // partials per row (K / kLnPartW)
-  float eps;
-};
-
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
@@ -70,117 +47,14 @@ __device__ __forceinline__ float wave_sum(float v) {
 // the last slice of the current one, so the epilogue overlaps the next tile's loads.
 // Within a round, the workgroups of one XCD (blockIdx % 8 equal) take consecutive
 // tiles, i.e. share A row panels in their L2.
-// LN_IN: the consumer side of LnArgs, as walk_tiles_hooked hooks.  Per tile, threads t <
-// BM load row m0 + t's partials with the tile's first slice (issue), merge them into
-// (mean, rstd) in LDS at that iteration's store phase (prepare; two slots by tile parity),
-// and every A slot is normalised on its registers before the LDS write (xform).  A slot's
-// row and 16-B chunk are fixed per thread (THREADS % F4_PER_ROW == 0), so gamma / beta are
-// one float4 each per slice, loaded with the slice.
-// MQ_LN_DIAG (measurement builds only): 1 = the hooks stage nothing (no partial / gamma /
-// beta loads, no normalisation: wrong results) - the hooked walker's own cost; 2 = loads
-// kept, normalisation skipped.
-#ifndef MQ_LN_DIAG
-#define MQ_LN_DIAG 0
-#endif
-#if MQ_LN_DIAG != 0 && !defined(MQ_MEASUREMENT_BUILD)
-#error "MQ_LN_DIAG computes wrong results: only a measurement build (-DMQ_MEASUREMENT_BUILD) may set it"
-#endif
-
-template <class T, class Coords>
-struct LnInHooks {
-  static constexpr int A_LOADS = T::BM * T::F4_PER_ROW / T::THREADS;
-  static_assert(T::A_SLOTS && T::THREADS % T::F4_PER_ROW == 0, "A slots: fixed row chunk per thread");
-  const LnArgs& ln;
-  Coords& coords;
-  float2* st;  // LDS [2][BM] (mean, rstd)
-  int M, nk, S;
-  float inv_k;
-  FastDiv nkd;
-  float2 part[kLnMaxParts];
-  floatx4 gg[T::PF], bb[T::PF];
-  float2 mr[A_LOADS];  // (mean, rstd) of this thread's A rows for the slice being stored
-  template <class DC>
-  __device__ __forceinline__ void issue(int s, DC) {
-    if constexpr (MQ_LN_DIAG == 1) return;
-    constexpr int d = DC::value;
-    const int sc = s < S ? s : S - 1;
-    const int i = nkd.div(sc), kt = sc - i * nk;
-    const int k = kt * T::BK + (threadIdx.x % T::F4_PER_ROW) * 4;
-    gg[d] = *reinterpret_cast<const floatx4*>(ln.g + k);
-    bb[d] = *reinterpret_cast<const floatx4*>(ln.b + k);
-    // (coords outside any per-thread branch: a tile origin computed under divergent control
-    // flow turns the staging's buffer descriptors into VGPRs - waterfall loops per load)
-    int m0;
-    int64_t n0;
-    coords(i, m0, n0);
-    // the partials of the fetched slice's tile rows, loaded with EVERY slice (64 B per
-    // thread from L2; rows past BM repeat): loaded only at tile starts, the registers
-    // would merge two values at the join and the copy would wait for the loads right there
-    const float2* src = reinterpret_cast<const float2*>(ln.stats_in) +
-                        (int64_t)min(m0 + (int)threadIdx.x % T::BM, M - 1) * kLnMaxParts;
-#pragma unroll
-    for (int t = 0; t < kLnMaxParts; ++t) part[t] = src[t];
-  }
-  __device__ __forceinline__ void prepare(int s) {
-    if constexpr (MQ_LN_DIAG == 1) return;
-    if (s >= S || nkd.mod(s) != 0) return;  // workgroup-uniform
-    // the merge must stay here, after the slice's MFMAs: left alone the compiler folds it
-    // into issue()'s equal-condition block and waits there for the partials' loads
-#pragma unroll
-    for (int t = 0; t < kLnMaxParts; ++t) asm volatile("" : "+v"(part[t].x), "+v"(part[t].y));
-    float mean = 0.f;
-#pragma unroll
-    for (int t = 0; t < kLnMaxParts; ++t) mean += part[t].x;
-    mean *= 1.0f / (float)kLnMaxParts;
-    float m2 = 0.f;
-#pragma unroll
-    for (int t = 0; t < kLnMaxParts; ++t) {
-      const float dm = part[t].x - mean;
-      m2 += part[t].y + (float)kLnPartW * dm * dm;
-    }
-    const float rstd = 1.0f / sqrtf(m2 * inv_k + ln.eps);
-    if (threadIdx.x < T::BM) st[(nkd.div(s) & 1) * T::BM + threadIdx.x] = make_float2(mean, rstd);
-  }
-  // at the top of the iteration that stores slice s: its rows' (mean, rstd) from LDS, read
-  // under the MFMAs
-  __device__ __forceinline__ void stage_in(int s) {
-    if constexpr (MQ_LN_DIAG == 1) return;
-    const float2* ms = st + (nkd.div(s < S ? s : S - 1) & 1) * T::BM;
-#pragma unroll
-    for (int a = 0; a < A_LOADS; ++a) mr[a] = ms[((int)threadIdx.x + a * T::THREADS) / T::F4_PER_ROW];
-  }
-  template <class DC>
-  __device__ __forceinline__ void xform(Stager<T>& sg, int s, DC) {
-    if constexpr (MQ_LN_DIAG != 0) return;
-    constexpr int d = DC::value;
-#pragma unroll
-    for (int a = 0; a < A_LOADS; ++a) sg.r[a] = (sg.r[a] - mr[a].x) * mr[a].y * gg[d] + bb[d];
-    const int sc = s < S ? s : S - 1;
-    const int i = nkd.div(sc), kt = sc - i * nk;
-    int m0;
-    int64_t n0;
-    coords(i, m0, n0);
-    if (n0 == 0 && s < S) {  // column-0 tiles: LN(A) rows out to x (workgroup-uniform)
-      const int ch = threadIdx.x % T::F4_PER_ROW;
-#pragma unroll
-      for (int a = 0; a < A_LOADS; ++a) {
-        // rows past M were staged from row M - 1 (clamped): they store row M - 1's own values
-        const int r = min(m0 + ((int)threadIdx.x + a * T::THREADS) / T::F4_PER_ROW, M - 1);
-        *reinterpret_cast<floatx4*>(ln.xout + (int64_t)r * ln.ldx + kt * T::BK + ch * 4) = sg.r[a];
-      }
-    }
-  }
-};
-
-template <class T, int EPI, bool LN_IN = false>
+template <class T, int EPI>
 __global__ __launch_bounds__(T::THREADS, T::WG_PER_CU) void gemm_nt_kernel(const float* __restrict__ A, int lda,
                                                          const float* __restrict__ W,
                                                          const float* __restrict__ bias,
                                                          const float* __restrict__ resid, int ldr,
                                                          float* __restrict__ out, int ldo, int M,
-                                                         int N, int K, LnArgs ln, int rx, LnFold lf) {
+                                                         int N, int K, int rx, LnFold lf) {
   __shared__ __attribute__((aligned(16))) float lds[2 * T::STAGE_FLOATS];
-  __shared__ float2 ln_st[LN_IN ? 2 * T::BM : 1];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave / T::WAVES_N, wn = wave % T::WAVES_N;
   const int tiles_n = (N + T::BN - 1) / T::BN, tiles_m = (M + T::BM - 1) / T::BM;
@@ -209,7 +83,6 @@ __global__ __launch_bounds__(T::THREADS, T::WG_PER_CU) void gemm_nt_kernel(const
     coords(i, m0, n0l);
     const int n0 = (int)n0l;
     if constexpr (T::M16) {  // 16x16 accumulator blocks (F32Tile::M16): K2p's store
-      static_assert(EPI != EPI_RESID_STATS, "no LayerNorm partials on the 16x16x32 tiles");
       floatx4 a4[2 * T::TM][2 * T::TN];
 #pragma unroll
       for (int m = 0; m < 2 * T::TM; ++m)
@@ -222,78 +95,6 @@ __global__ __launch_bounds__(T::THREADS, T::WG_PER_CU) void gemm_nt_kernel(const
       return;
     }
     static_assert(T::M16 || EPI < EPI_RESID_LN_STATS, "the LayerNorm-fold epilogues are on the 16x16 store");
-    if constexpr (EPI == EPI_RESID_STATS) {
-      // y = acc + bias + resid, then per row the partial (mean, M2) of y over the wave
-      // tile's WN = kLnPartW columns: the 32 lanes of a lane half hold a row's columns
-      // (tn-major), reduced by xor shuffles within the half.  Full tiles load the residual
-      // and store y by buffer ops off the wave tile's origin with scalar row offsets (as the
-      // EPI_RESID path below); a ragged last row band uses guarded plain accesses.
-      static_assert(T::WN == kLnPartW, "stats partials are per kLnPartW-column wave tile");
-      const int wr0 = m0 + wm * T::WM, wc0 = n0 + wn * T::WN;
-      const int part = wc0 / T::WN;
-      float bv[T::TN];
-#pragma unroll
-      for (int tn = 0; tn < T::TN; ++tn) bv[tn] = bias[wc0 + tn * 32 + (lane & 31)];
-      float rv[T::TM][T::TN][16];
-      const bool full = m0 + T::BM <= M;
-      const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-          (void*)(out + (int64_t)wr0 * ldo + wc0), (short)0, 0x7fffffff, 0x00020000);
-      const int ol = (4 * (lane >> 5) * ldo + (lane & 31)) * 4;
-      if (full) {
-        const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(resid + (int64_t)wr0 * ldr + wc0), (short)0, 0x7fffffff, 0x00020000);
-        const int rl = (4 * (lane >> 5) * ldr + (lane & 31)) * 4;
-#pragma unroll
-        for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-          for (int tn = 0; tn < T::TN; ++tn)
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-              rv[tm][tn][e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-                  rr, rl, (acc_row(tm, e, 0) * ldr + tn * 32) * 4, 0));
-      } else {
-#pragma unroll
-        for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-          for (int tn = 0; tn < T::TN; ++tn)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-              const int row = min(wr0 + acc_row(tm, e, lane), M - 1);
-              rv[tm][tn][e] = resid[(int64_t)row * ldr + wc0 + tn * 32 + (lane & 31)];
-            }
-      }
-#pragma unroll
-      for (int tm = 0; tm < T::TM; ++tm)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int row = wr0 + acc_row(tm, e, lane);
-          float v[T::TN], sum = 0.f;
-#pragma unroll
-          for (int tn = 0; tn < T::TN; ++tn) {
-            v[tn] = acc[tm][tn][e] + bv[tn] + rv[tm][tn][e];
-            sum += v[tn];
-          }
-          if (full) {
-#pragma unroll
-            for (int tn = 0; tn < T::TN; ++tn)
-              __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[tn]), ro, ol, (acc_row(tm, e, 0) * ldo + tn * 32) * 4, 0);
-          } else if (row < M) {
-#pragma unroll
-            for (int tn = 0; tn < T::TN; ++tn) out[(int64_t)row * ldo + wc0 + tn * 32 + (lane & 31)] = v[tn];
-          }
-#pragma unroll
-          for (int off = 16; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
-          const float mean = sum * (1.0f / T::WN);
-          float m2 = 0.f;
-#pragma unroll
-          for (int tn = 0; tn < T::TN; ++tn) m2 += (v[tn] - mean) * (v[tn] - mean);
-#pragma unroll
-          for (int off = 16; off > 0; off >>= 1) m2 += __shfl_xor(m2, off);
-          if ((lane & 31) == 0 && row < M)
-            reinterpret_cast<float2*>(ln.stats_out)[(int64_t)row * ln.nt + part] = make_float2(mean, m2);
-        }
-      return;
-    }
     if (m0 + T::BM <= M && n0 + T::BN <= N) {
       // full tile: every bias / residual load goes out before the first use, so the
       // tile pays one memory round trip (the guarded loop below waits per element).
@@ -354,117 +155,7 @@ __global__ __launch_bounds__(T::THREADS, T::WG_PER_CU) void gemm_nt_kernel(const
         }
     }
   };
-  if constexpr (LN_IN) {
-    LnInHooks<T, decltype(coords)> hk{ln, coords, ln_st, M, K / T::BK, n_tiles * (K / T::BK), 1.0f / (float)K,
-                                      FastDiv(K / T::BK)};
-    walk_tiles_hooked<T>(lds, n_tiles, TileOperands{A, lda, M, W, K, N, K}, coords, epi, hk);
-  } else {
-    walk_tiles<T>(lds, n_tiles, TileOperands{A, lda, M, W, K, N, K}, coords, epi);
-  }
-}
-
-// ------------------------------------------- K4 / K6: residual GEMM + LayerNorm ---
-// x = LN(A W^T + bias + resid) with the LayerNorm in the epilogue: a workgroup owns 32 FULL
-// rows (BN = N = H, T = F32Tile<1, 8, 1, H / 256, ..., BK 16>: 8 waves x 32 x (H/8)
-// columns, 16-deep slices so the 32 + H row image double-buffers in LDS), so each row's
-// mean and variance are block reductions - no y round trip through HBM and no LayerNorm
-// launch (24 per batched step).  Two-pass statistics over the fp32 sums as ln_kernel
-// computes them (the summation order differs: results agree to rounding).  `out` may be
-// `resid` (each element is read and written by the same thread, and a workgroup owns its
-// rows); the strided CLS-only layer, whose compact output rows alias other residual rows,
-// keeps the two-launch path.  Persistent: workgroups walk row blocks t = blockIdx.x + i G.
-template <class T>
-__global__ __launch_bounds__(T::THREADS, 1) void gemm_resid_ln_kernel(
-    const float* __restrict__ A, int lda, const float* __restrict__ W, const float* __restrict__ bias,
-    const float* resid, const float* __restrict__ lng, const float* __restrict__ lnb, float eps, float* out,
-    int M, int K) {
-  constexpr int H = T::BN;
-  static_assert(T::WAVES_M == 1 && T::TM == 1 && T::BM == 32, "32-row full-width tiles");
-  __shared__ __attribute__((aligned(16))) float lds[2 * T::STAGE_FLOATS];
-  __shared__ float red[2][T::WAVES_N][32];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int total = (M + 31) / 32;
-  const int n_tiles = blockIdx.x < total ? (total - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
-  auto coords = [&](int i, int& m0, int64_t& n0) {
-    m0 = (blockIdx.x + i * gridDim.x) * 32;
-    n0 = 0;
-  };
-  // this lane's columns: wave w, tile tn, lane & 31; bias / gamma / beta held for the launch
-  float bv[T::TN], gv[T::TN], ev[T::TN];
-#pragma unroll
-  for (int tn = 0; tn < T::TN; ++tn) {
-    const int col = wave * T::WN + tn * 32 + (lane & 31);
-    bv[tn] = bias[col];
-    gv[tn] = lng[col];
-    ev[tn] = lnb[col];
-  }
-  auto epi = [&](int i, floatx16(&acc)[T::TM][T::TN], float*) {
-    const int m0 = (blockIdx.x + i * gridDim.x) * 32;
-    // v = acc + bias + resid (rows past M read row M - 1 and are never stored)
-#pragma unroll
-    for (int tn = 0; tn < T::TN; ++tn) {
-      const int col = wave * T::WN + tn * 32 + (lane & 31);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = min(m0 + acc_row(0, e, lane), M - 1);
-        acc[0][tn][e] = acc[0][tn][e] + bv[tn] + resid[(int64_t)row * H + col];
-      }
-    }
-    // row sums: this lane's T::TN columns, then the 32 lanes of its half (same rows), then
-    // the waves through LDS; element e of lane half h is row (e&3) + 8(e>>2) + 4h
-    auto row_reduce = [&](int pass, auto&& val) {
-      float p[16];
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        float t = 0.f;
-#pragma unroll
-        for (int tn = 0; tn < T::TN; ++tn) t += val(tn, e);
-        p[e] = t;
-      }
-#pragma unroll
-      for (int off = 1; off < 32; off <<= 1)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) p[e] += __shfl_xor(p[e], off);
-      if ((lane & 31) == 0)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) red[pass][wave][acc_row(0, e, lane)] = p[e];
-    };
-    row_reduce(0, [&](int tn, int e) { return acc[0][tn][e]; });
-    __syncthreads();
-    float mean[16];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int rr = acc_row(0, e, lane);
-      float t = 0.f;
-#pragma unroll
-      for (int w = 0; w < T::WAVES_N; ++w) t += red[0][w][rr];
-      mean[e] = t * (1.0f / H);
-    }
-    row_reduce(1, [&](int tn, int e) {
-      const float d = acc[0][tn][e] - mean[e];
-      return d * d;
-    });
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int rr = acc_row(0, e, lane);
-      float t = 0.f;
-#pragma unroll
-      for (int w = 0; w < T::WAVES_N; ++w) t += red[1][w][rr];
-      const float rstd = 1.0f / sqrtf(t * (1.0f / H) + eps);
-      const int row = m0 + rr;
-      if (row < M) {
-#pragma unroll
-        for (int tn = 0; tn < T::TN; ++tn) {
-          const int col = wave * T::WN + tn * 32 + (lane & 31);
-          out[(int64_t)row * H + col] = (acc[0][tn][e] - mean[e]) * rstd * gv[tn] + ev[tn];
-        }
-      }
-    }
-    // (the next tile's reductions reuse red[]: its first write follows a block barrier
-    // inside the slice loop, after every wave has read this tile's sums)
-  };
-  walk_tiles<T>(lds, n_tiles, TileOperands{A, lda, M, W, K, H, K}, coords, epi);
+  walk_tiles<T>(lds, n_tiles, TileOperands{A, lda, M, W, K, N, K}, coords, epi);
 }
 
 // ---------------------------------------------------------- split-K GEMM ------
@@ -1129,6 +820,8 @@ __global__ __launch_bounds__(256) void ln_kernel(const float* __restrict__ src, 
     }
   }
 }
+// The forward's RPW (1 / 2 / 4 measured 0.38 / 0.31 / 0.30 ms per step: DESIGN.md section 4).
+constexpr int kLnRowsPerWave = 4;
 
 // LayerNorm of `rows` rows `stride` floats apart, in place (a wave holds its whole row before
 // it writes): the B CLS rows of the raw y that the CLS-only last layer reads normalised when
@@ -2055,15 +1748,15 @@ struct GemmArgs {
   bool former_epi = false;   // K2p: the single-wave GELU epilogue (MQ_ENC_OPT_EPI_SPLIT 0)
 };
 
-template <class T, int EPI, bool LN_IN = false>
-void launch_gemm_t(const GemmArgs& g, int num_cus, hipStream_t s, const LnArgs& ln = LnArgs{}) {
+template <class T, int EPI>
+void launch_gemm_t(const GemmArgs& g, int num_cus, hipStream_t s) {
   const int tiles = ((g.M + T::BM - 1) / T::BM) * ((g.N + T::BN - 1) / T::BN);
   // persistent grid: the workgroups that fit the CUs at once, a multiple of 8
   const int grid = (std::min(tiles, T::WG_PER_CU * num_cus) + 7) / 8 * 8;
   const int tiles_m = (g.M + T::BM - 1) / T::BM, tiles_n = (g.N + T::BN - 1) / T::BN;
   const int rx = region_pick_rx(tiles_m, tiles_n, (double)T::BM * g.K * 4, (double)T::BN * g.K * 4, grid);
-  hipLaunchKernelGGL((gemm_nt_kernel<T, EPI, LN_IN>), dim3(grid), dim3(T::THREADS), 0, s, g.A, g.lda, g.W,
-                     g.bias, g.resid, g.ldr, g.out, g.ldo, g.M, g.N, g.K, ln, rx, g.lf);
+  hipLaunchKernelGGL((gemm_nt_kernel<T, EPI>), dim3(grid), dim3(T::THREADS), 0, s, g.A, g.lda, g.W,
+                     g.bias, g.resid, g.ldr, g.out, g.ldo, g.M, g.N, g.K, rx, g.lf);
 }
 
 using GemmBig = F32Tile<2, 2, 2, 2>;    // 128 x 128
@@ -2225,26 +1918,6 @@ void launch_gemm(const GemmArgs& g, int num_cus, hipStream_t s, bool x6 = false,
   launch_gemm_tile<EPI>(g, best, num_cus, s);
 }
 
-// LayerNorm deferred into the consumer (LnArgs): the producer is the 128x96 tile (its wave
-// tile is the partial width), the consumer the 128x128 or 128x96 tile by launch_gemm's
-// waste model over those two.
-void launch_gemm_stats(const GemmArgs& g, const LnArgs& ln, int num_cus, hipStream_t s) {
-  launch_gemm_t<GemmT96, EPI_RESID_STATS>(g, num_cus, s, ln);
-}
-
-template <int EPI>
-void launch_gemm_ln_in(const GemmArgs& g, const LnArgs& ln, int num_cus, hipStream_t s) {
-  const int64_t slots = 2 * (int64_t)num_cus;
-  auto cost = [&](int bn, double eff) {
-    const int64_t tiles = (int64_t)((g.M + 127) / 128) * ((g.N + bn - 1) / bn);
-    return (double)((tiles + slots - 1) / slots) * 128 * bn / eff;
-  };
-  if (cost(128, 1.0) <= cost(96, 0.96))
-    launch_gemm_t<GemmBig, EPI, true>(g, num_cus, s, ln);
-  else
-    launch_gemm_t<GemmT96, EPI, true>(g, num_cus, s, ln);
-}
-
 // MQ_ENC_OPT_LN_FOLD's default (DESIGN.md section 4 has the A/B that decides it)
 #ifndef MQ_LN_FOLD_DEFAULT
 #define MQ_LN_FOLD_DEFAULT 1
@@ -2304,17 +1977,12 @@ struct mq_encoder {
   int rows_splits = 0;          // few-row FFN-down K splits (0 = automatic)
   int splitk_max = 16;          // deepest split-K of the tiled path's few-row GEMMs
   int splitk_tiles = 0;         // split-K only grids of <= this many 32x128 tiles (0 = num_cus)
-  int ln_rows_per_wave = 4;     // batched LayerNorm kernel: rows per wave
-  bool fused_ln = false;        // batched residual GEMMs: LayerNorm in the epilogue (full-row tiles;
-                                // measured slower, kept as an option: DESIGN.md §4)
   int resident_layers = 8;      // few-row forward: layers whose weights load with the default
                                 // cache policy (8 x 28 MB of BERT-base fit the 256 MB MALL);
                                 // later layers' loads are non-temporal
-  bool ln_on_load = false;      // batched forward: LayerNorm applied by the consuming GEMM (LnArgs;
-                                // measured slower: the consumers' staging VALU)
-  Buf lnst;                     // its per-row partials, two sets of [M][H / kLnPartW] (mean, M2)
   bool x6_presplit = true;      // split-f32 batched GEMMs on the W3 images (K2p)
   bool ln_fold = kLnFoldDefault;  // split-f32 batched forward: LayerNorm folded into the GEMMs (LnFold)
+  Buf lnst;                     // its per-row partials, two sets of [M][H / kLnPartW] (mean, M2)
   Buf wfold3, wfoldf, sfold;    // its gamma-scaled weights (W3 images / fp32) and s, c vectors
   bool rows_planes = false;     // few-row forward: keep the two-plane hand-offs (no FL_ACC merge)
   bool cls_kfree = kClsKfreeDefault;  // CLS pooling, batched forward: the last layer without K / V
@@ -2485,21 +2153,7 @@ template <int VPL>
 void gemm_resid_ln(mq_encoder* e, const GemmArgs& g, const float* lng, const float* lnb, float* x,
                    int stage, hipStream_t s) {
   const int H = VPL * 256;
-  const unsigned rb = (unsigned)((g.M + 3) / 4);
   const int S = splitk_factor(g, e->num_cus, e->splitk_max, e->splitk_tiles);
-  if constexpr (VPL <= 3) {  // (the 32 + H row image of hidden 1024 does not double-buffer in LDS)
-    // full-row tiles with the LayerNorm in the epilogue: exact f32, unit-stride residual
-    // rows written in place (the strided CLS-only layer's compact output would overwrite
-    // residual rows other workgroups still read)
-    if (!S && e->fused_ln && e->precision == MQ_DTYPE_F32 && g.ldr == H && g.N == H && g.resid == x) {
-      using T = F32Tile<1, 8, 1, VPL, false, 2, false, 16>;
-      e->tl.mark(s, stage);
-      const int tiles = (g.M + 31) / 32;
-      hipLaunchKernelGGL((gemm_resid_ln_kernel<T>), dim3(std::min(tiles, e->num_cus)), dim3(T::THREADS), 0, s,
-                         g.A, g.lda, g.W, g.bias, g.resid, lng, lnb, e->cfg.ln_eps, x, g.M, g.K);
-      return;
-    }
-  }
   if (S && g.ldr == H && g.N == H) {
     e->tl.mark(s, stage);
     launch_splitk_gemm(g, S, s);
@@ -2510,15 +2164,9 @@ void gemm_resid_ln(mq_encoder* e, const GemmArgs& g, const float* lng, const flo
   }
   gemm<EPI_RESID>(e, g, stage, s);
   e->tl.mark(s, ST_LN);
-  const int rpw = e->ln_rows_per_wave;  // MQ_ENC_OPT_LN_ROWS_PER_WAVE: 1 / 2 / 4
-  if (rpw == 4)
-    hipLaunchKernelGGL((ln_kernel<VPL, 4>), dim3((unsigned)((g.M + 15) / 16)), dim3(256), 0, s, g.out, g.M, lng,
-                       lnb, e->cfg.ln_eps, x);
-  else if (rpw == 1)
-    hipLaunchKernelGGL((ln_kernel<VPL, 1>), dim3(rb), dim3(256), 0, s, g.out, g.M, lng, lnb, e->cfg.ln_eps, x);
-  else
-    hipLaunchKernelGGL((ln_kernel<VPL, 2>), dim3((unsigned)((g.M + 7) / 8)), dim3(256), 0, s, g.out, g.M, lng,
-                       lnb, e->cfg.ln_eps, x);
+  constexpr int rows = 4 * kLnRowsPerWave;  // per 256-thread block
+  hipLaunchKernelGGL((ln_kernel<VPL, kLnRowsPerWave>), dim3((unsigned)((g.M + rows - 1) / rows)), dim3(256), 0, s,
+                     g.out, g.M, lng, lnb, e->cfg.ln_eps, x);
 }
 
 // The CLS_KFREE last layer's buffers inside mq_encoder::cls for B sequences.
@@ -2612,19 +2260,12 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* types, const int* mask
   e->tl.mark(s, ST_EMBED);
   hipLaunchKernelGGL((embed_ln_kernel<VPL>), dim3(row_blocks), dim3(256), 0, s, ids, M, L,
                      c.vocab_size, e->word, e->pos, e->typ, types, c.type_vocab, e->eg, e->eb, c.ln_eps, e->x.p);
-  // LayerNorm deferred into the consumers (LnArgs) on the full-M layers: exact f32, rows
-  // enough for the tiled path, hidden a whole number of kLnPartW-column partials
-  const int nt = H / kLnPartW;
-  const bool lnl = e->ln_on_load && !e->fused_ln && e->precision == MQ_DTYPE_F32 && M > 256 &&
-                   H == kLnPartW * kLnMaxParts && e->lnst.n >= (size_t)4 * M * nt;
-  float* st1 = e->lnst.p;                          // out-proj -> FFN-up
-  float* st2 = lnl ? e->lnst.p + (size_t)2 * M * nt : nullptr;  // FFN-down -> next QKV
-  bool y_pending = false;  // x holds LN2's input y (+ st2) instead of the LayerNorm output
   const LayerW* prev = nullptr;
   // LayerNorm folded into the split-f32 GEMMs (LnFold) on the full-M layers: every one of
   // their GEMMs on the split-f32 tiles (launch_gemm's fill-the-chip test at the narrowest, N
   // = H), the folded weights built.  x and y are then the two raw-y buffers: out-proj writes
-  // y (+ st1), FFN-down x (+ st2), each reading the other as its residual.
+  // y (+ fst1), FFN-down x (+ fst2), each reading the other as its residual.
+  const int nt = H / kLnPartW;  // partials per row
   const LayerW w0 = e->layers.empty() ? LayerW{} : e->layers[0];
   const bool fold = e->ln_fold && e->precision == MQ_DTYPE_F32X6 && M > 256 && H == kLnPartW * kLnMaxParts &&
                     F % 32 == 0 && (int64_t)((M + 127) / 128) * ((H + 191) / 192) >= e->num_cus &&
@@ -2640,7 +2281,7 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* types, const int* mask
   // On the re-split tiles (x6_presplit 0) the QKV GEMM runs as it did and the epilogue's
   // attention follows as a launch of its own (launch_attn32): x6_presplit 0 / 1 give the same bits.
   const bool attn_shape = e->qkv_attn && e->precision == MQ_DTYPE_F32X6 && L == 32 && H == 64 * c.heads &&
-                          H % 192 == 0 && H % 32 == 0 && M > 256 && !lnl &&
+                          H % 192 == 0 && H % 32 == 0 && M > 256 &&
                           (int64_t)((M + 127) / 128) * ((3 * H + 191) / 192) >= e->num_cus &&
                           x6p_pick_tile(M, 3 * H, e->num_cus) == 0 && (int64_t)M * H < (1ll << 29);
   const bool qkv_attn = attn_shape && e->x6_presplit;
@@ -2650,23 +2291,6 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* types, const int* mask
     g.former_epi = !e->epi_split;
     g.lf.eps = c.ln_eps;
     launch_gemm_fold<decltype(epi)::value>(g, e->num_cus, s);
-  };
-  auto ln_args = [&](const float* stats, const float* g, const float* b) {
-    LnArgs a{};
-    a.stats_in = stats;
-    a.g = g;
-    a.b = b;
-    a.xout = e->x.p;
-    a.ldx = H;
-    a.nt = nt;
-    a.eps = c.ln_eps;
-    return a;
-  };
-  auto stats_out = [&](float* stats) {
-    LnArgs a{};
-    a.stats_out = stats;
-    a.nt = nt;
-    return a;
   };
   for (size_t li = 0; li < e->layers.size(); ++li) {
     const LayerW& w = e->layers[li];
@@ -2679,9 +2303,6 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* types, const int* mask
     // the last layer without K / V (cls_pass_kernel holds hidden <= 768 in LDS)
     const bool kfree = cls_only && L > 1 && e->cls_kfree && VPL <= 3 && e->wkt.p != nullptr &&
                        e->cls.n >= ClsBufs::floats(B, H, c.heads);
-    // QKV input: x, or (deferred LN2 of the previous layer) y normalised while staged,
-    // the column-0 tiles writing LN2(y) to x for the residual and the CLS-row Q GEMM
-    const float* qkv_in = y_pending ? e->y.p : e->x.p;
     // few rows (single queries past the few-row limit): the layers past resident_layers
     // stream their weights non-temporally in the split-K GEMMs (as forward_rows does)
     const int lnt = M <= 256 && (int)li >= e->resident_layers ? 1 : 0;
@@ -2700,21 +2321,17 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* types, const int* mask
     };
     auto qkv_gemm = [&](GemmArgs g) {
       g.nt = lnt;
-      if (raw) {
+      if (raw)
         qkv_fold(g, (int)(g.W - w.wqkv) / H);
-      } else if (y_pending) {
-        e->tl.mark(s, ST_QKV);
-        launch_gemm_ln_in<EPI_BIAS>(g, ln_args(st2, prev->ln2g, prev->ln2b), e->num_cus, s);
-      } else {
+      else
         gemm<EPI_BIAS>(e, g, ST_QKV, s);
-      }
     };
     if (kfree) {
       const ClsBufs cb(e->cls.p, B, H, c.heads);
       // the layer's input as the pass reads it: normalised rows in x, or raw rows with their
-      // partials and the previous layer's LN2 (the fold's x + fst2, LN-on-load's y + st2)
-      const float* xin = raw ? e->x.p : y_pending ? e->y.p : e->x.p;
-      const float* xst = raw ? fst2 : y_pending ? st2 : nullptr;
+      // partials and the previous layer's LN2 (the fold's x + fst2)
+      const float* xin = e->x.p;
+      const float* xst = raw ? fst2 : nullptr;
       if (xst) {
         // The normalised CLS rows go to a SEPARATE [B, H] buffer (the Q GEMM and the tail's
         // residual read that): row b L of the raw buffer stays raw for the pass below.
@@ -2735,7 +2352,7 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* types, const int* mask
     } else if (cls_only && L > 1) {
       // only the CLS rows need queries: K and V for every token ([M, 2H] into qkv columns
       // H..3H), Q for the B CLS rows (every L-th row of x into row b*L of qkv)
-      GemmArgs kv{e->slab.p, e->slab.n, qkv_in, H, w.wqkv + (int64_t)H * H, w.bqkv + H, nullptr, 0, e->qkv.p + H,
+      GemmArgs kv{e->slab.p, e->slab.n, e->x.p, H, w.wqkv + (int64_t)H * H, w.bqkv + H, nullptr, 0, e->qkv.p + H,
                   3 * H, M, 2 * H, H};
       if (w.wqkv3) kv.W3 = w.wqkv3 + w3_row_offset(H, H);
       qkv_gemm(kv);
@@ -2750,7 +2367,7 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* types, const int* mask
     } else if (qkv_attn && (raw ? w.wqkvg3 != nullptr : w.wqkv3 != nullptr)) {
       // L = 32 attention in the QKV GEMM's epilogue (EPI_ATTN_*): ctx straight from the
       // accumulators, no qkv written and no attention launch; folded or not as the plain QKV is
-      X6pArgs a{qkv_in, H, raw ? w.wqkvg3 : w.wqkv3, raw ? w.wqkvc : w.bqkv, nullptr, 0, e->ctx.p, H, M, 3 * H, H};
+      X6pArgs a{e->x.p, H, raw ? w.wqkvg3 : w.wqkv3, raw ? w.wqkvc : w.bqkv, nullptr, 0, e->ctx.p, H, M, 3 * H, H};
       if (raw) {
         a.lf.s = w.wqkvs;
         a.lf.stats_in = fst2;
@@ -2762,12 +2379,11 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* types, const int* mask
       launch_gemm_x6p(a, raw ? EPI_ATTN_LNFOLD : EPI_ATTN_BIAS, 0, e->num_cus, s);
       attn_done = true;
     } else {
-      GemmArgs qkv{e->slab.p, e->slab.n, qkv_in, H, w.wqkv, w.bqkv, nullptr, 0, e->qkv.p, 3 * H, M, 3 * H, H};
+      GemmArgs qkv{e->slab.p, e->slab.n, e->x.p, H, w.wqkv, w.bqkv, nullptr, 0, e->qkv.p, 3 * H, M, 3 * H, H};
       qkv.W3 = w.wqkv3;
       qkv_gemm(qkv);
       attn_after = attn_shape;
     }
-    y_pending = false;
     const bool resid_raw = raw && fold_layer;  // (the tail's residual rows were normalised above)
     raw = false;
     if (!kfree && !attn_done) {
@@ -2778,8 +2394,7 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* types, const int* mask
       else
         launch_attention(B, L, c.heads, qt, H, scale, e->qkv.p, mask, e->ctx.p, s);
     }
-    const bool lnl_layer = lnl && !cls_only;
-    // x = LN1(x + ctx Wo^T + bo)  (compact [rows, H], through y) - or, deferred, y + partials
+    // x = LN1(x + ctx Wo^T + bo)  (compact [rows, H], through y)
     GemmArgs oproj{e->slab.p, e->slab.n, e->ctx.p, stride, w.wo, w.bo, resid, ldr, e->y.p, H, rows, H, H, lnt};
     oproj.W3 = w.wo3;
     if (fold_layer) {  // y = ctx Wo^T + bo + (LN2_prev(x) or x), raw, + its partials
@@ -2790,14 +2405,10 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* types, const int* mask
         oproj.lf.b = prev->ln2b;
       }
       fold_gemm(IC<EPI_RESID_LN_STATS>{}, oproj, ST_OPROJ);
-    } else if (lnl_layer) {
-      e->tl.mark(s, ST_OPROJ);
-      launch_gemm_stats(oproj, stats_out(st1), e->num_cus, s);
     } else {
       gemm_resid_ln<VPL>(e, oproj, w.ln1g, w.ln1b, e->x.p, ST_OPROJ, s);
     }
-    GemmArgs up{e->slab.p, e->slab.n, lnl_layer ? e->y.p : e->x.p, H, w.w1, w.b1, nullptr, 0, e->ffn.p, F,
-                rows, F, H, lnt};
+    GemmArgs up{e->slab.p, e->slab.n, e->x.p, H, w.w1, w.b1, nullptr, 0, e->ffn.p, F, rows, F, H, lnt};
     up.W3 = w.w13;
     if (fold_layer) {  // FFN-up on the raw y with LN1 folded in
       up.A = e->y.p;
@@ -2810,12 +2421,6 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* types, const int* mask
         fold_gemm(IC<EPI_GELU_TANH_LNFOLD>{}, up, ST_FFN_UP);
       else
         fold_gemm(IC<EPI_GELU_ERF_LNFOLD>{}, up, ST_FFN_UP);
-    } else if (lnl_layer) {  // FFN-up normalises y (LN1) while staging; its column-0 tiles write x
-      e->tl.mark(s, ST_FFN_UP);
-      if (c.gelu == MQ_GELU_TANH)
-        launch_gemm_ln_in<EPI_GELU_TANH>(up, ln_args(st1, w.ln1g, w.ln1b), e->num_cus, s);
-      else
-        launch_gemm_ln_in<EPI_GELU_ERF>(up, ln_args(st1, w.ln1g, w.ln1b), e->num_cus, s);
     } else if (c.gelu == MQ_GELU_TANH) {
       gemm<EPI_GELU_TANH>(e, up, ST_FFN_UP, s);
     } else {
@@ -2834,15 +2439,12 @@ int forward_vpl(mq_encoder* e, const int* ids, const int* types, const int* mask
       fold_gemm(IC<EPI_RESID_LN_STATS>{}, down, ST_FFN_DOWN);
       if (last) {
         e->tl.mark(s, ST_LN);
-        hipLaunchKernelGGL((ln_kernel<VPL, 4>), dim3((unsigned)((M + 15) / 16)), dim3(256), 0, s, e->ctx.p, M, w.ln2g,
-                           w.ln2b, c.ln_eps, e->x.p);
+        constexpr int wg_rows = 4 * kLnRowsPerWave;
+        hipLaunchKernelGGL((ln_kernel<VPL, kLnRowsPerWave>), dim3((unsigned)((M + wg_rows - 1) / wg_rows)), dim3(256),
+                           0, s, e->ctx.p, M, w.ln2g, w.ln2b, c.ln_eps, e->x.p);
       } else {
         raw = true;
       }
-    } else if (lnl_layer && li + 1 < e->layers.size()) {  // LN2 deferred into the next layer's QKV
-      e->tl.mark(s, ST_FFN_DOWN);
-      launch_gemm_stats(down, stats_out(st2), e->num_cus, s);
-      y_pending = true;
     } else if (kfree) {  // the encoder's end: LN2, CLS pooling and the L2 norm with the reduction
       gemm_resid_ln_pool<VPL>(e, down, w.ln2g, w.ln2b, mask, out, raw_cls, ST_FFN_DOWN, s);
       pooled = true;
@@ -3661,25 +3263,13 @@ int mq_encoder_set_option(mq_encoder* e, int option, int value) {
       MQ_CHECK_ARG(value >= 2 && value <= 64, "splitk_max must be in [2, 64] (got %d)", value);
       e->splitk_max = value;
       break;
-    case MQ_ENC_OPT_LN_ROWS_PER_WAVE:
-      MQ_CHECK_ARG(value == 1 || value == 2 || value == 4, "ln_rows_per_wave must be 1, 2 or 4 (got %d)", value);
-      e->ln_rows_per_wave = value;
-      break;
     case MQ_ENC_OPT_FUSE_ATTN_OPROJ:
       MQ_CHECK_ARG(value == 0 || value == 1, "fuse_attn_oproj must be 0 or 1 (got %d)", value);
       e->fuse_attn_oproj = value != 0;
       break;
-    case MQ_ENC_OPT_FUSED_LN:
-      MQ_CHECK_ARG(value == 0 || value == 1, "fused_ln must be 0 or 1 (got %d)", value);
-      e->fused_ln = value != 0;
-      break;
     case MQ_ENC_OPT_RESIDENT_LAYERS:
       MQ_CHECK_ARG(value >= 0 && value <= 1024, "resident_layers must be in [0, 1024] (got %d)", value);
       e->resident_layers = value;
-      break;
-    case MQ_ENC_OPT_LN_ON_LOAD:
-      MQ_CHECK_ARG(value == 0 || value == 1, "ln_on_load must be 0 or 1 (got %d)", value);
-      e->ln_on_load = value != 0;
       break;
     case MQ_ENC_OPT_SPLITK_TILES:
       MQ_CHECK_ARG(value >= 0 && value <= 4096, "splitk_tiles must be in [0, 4096] (got %d)", value);
@@ -3725,10 +3315,7 @@ int mq_encoder_get_option(const mq_encoder* e, int option, int* value) {
     case MQ_ENC_OPT_ROWS_MAX: *value = e->rows_max; break;
     case MQ_ENC_OPT_ROWS_SPLITS: *value = e->rows_splits; break;
     case MQ_ENC_OPT_SPLITK_MAX: *value = e->splitk_max; break;
-    case MQ_ENC_OPT_LN_ROWS_PER_WAVE: *value = e->ln_rows_per_wave; break;
     case MQ_ENC_OPT_FUSE_ATTN_OPROJ: *value = e->fuse_attn_oproj ? 1 : 0; break;
-    case MQ_ENC_OPT_FUSED_LN: *value = e->fused_ln ? 1 : 0; break;
-    case MQ_ENC_OPT_LN_ON_LOAD: *value = e->ln_on_load ? 1 : 0; break;
     case MQ_ENC_OPT_RESIDENT_LAYERS: *value = e->resident_layers; break;
     case MQ_ENC_OPT_SPLITK_TILES: *value = e->splitk_tiles; break;
     case MQ_ENC_OPT_X6_PRESPLIT: *value = e->x6_presplit ? 1 : 0; break;
@@ -3777,7 +3364,7 @@ int ensure_forward_bufs(mq_encoder* e, int B, int L) {
   // y also holds the few-row forward's output-projection planes (<= 4 of M rows)
   rc = build_fold(e);  // (MQ_ENC_OPT_LN_FOLD: the folded weights of the current mode, once)
   if (rc) return rc;
-  const size_t ln_parts = (e->ln_on_load || e->ln_fold) && M > 256 ? (size_t)4 * M * std::max(1, c.hidden / kLnPartW) : 0;
+  const size_t ln_parts = e->ln_fold && M > 256 ? (size_t)4 * M * std::max(1, c.hidden / kLnPartW) : 0;
   // (MQ_ENC_OPT_CLS_KFREE: the last layer's CLS-row buffers)
   const size_t cls_floats = e->cls_kfree && c.pooling == MQ_POOL_CLS && L > 1 ? ClsBufs::floats(B, c.hidden, c.heads) : 0;
   for (auto bn : {std::make_pair(&e->x, M * c.hidden), std::make_pair(&e->y, (M <= (size_t)kRowsMax ? 4 : 1) * M * c.hidden),

@@ -8,8 +8,6 @@
 
 namespace mq {
 
-// EPI_RESID_STATS: EPI_RESID that also leaves per-row LayerNorm partials of its output
-// (encoder.hip, LnArgs: the LayerNorm is then applied by the consuming GEMM).
 // LayerNorm folded into the split-f32 GEMMs (LnFold, gemm_x6p.hpp; 16x16 store only):
 // EPI_RESID_LN_STATS is the producer, out = acc + bias + LN(resid) plus the partials of out;
 // the *_LNFOLD kinds are the consumers, out = epi(rho_r (acc - mu_r s[col]) + c[col]) with
@@ -19,7 +17,7 @@ enum Epi {
   EPI_GELU_ERF = 1,
   EPI_GELU_TANH = 2,
   EPI_RESID = 3,
-  EPI_RESID_STATS = 4,
+  // 4: retired, never reuse
   EPI_RESID_LN_STATS = 5,
   EPI_BIAS_LNFOLD = 6,
   EPI_GELU_ERF_LNFOLD = 7,

@@ -61,8 +61,10 @@ struct F32Tile {
   static constexpr int BM = WAVES_M * WM, BN = WAVES_N * WN;
   static constexpr int THREADS = WAVES_M * WAVES_N * kWave;
   static constexpr int ROWS = BM + BN;
-  // K per staged slice: 32 (exact f32 / bf16 default), 16 (split f32; or an exact-f32 tile
-  // whose B panel is too tall for two 32-deep stages, e.g. the full-row 32 x 768 tile)
+  // K per staged slice: 32 (exact f32 / bf16, split f32 M16), 16 (split f32 on the 32x32
+  // MFMA).  BK_ overrides it; no tile sets it any more (its one user was the retired
+  // full-row 32 x H tile), and it stays only because removing it renames every F32Tile
+  // kernel: a follow-up.
   static constexpr int BK = BK_ ? BK_ : (X6 && !M16 ? 16 : 32);
   static_assert(BK == 32 || (BK == 16 && !BF16), "slice depth 32, or 16 for the f32 forms");
   static constexpr int F4_PER_ROW = BK / 4;               // float4 per row per slice
@@ -79,8 +81,7 @@ struct F32Tile {
   // (an M16 tile's two 32-deep stages of 208-B rows take 91-104 KB: one per CU)
   static constexpr int WG_PER_CU = THREADS == 256 && !M16 ? 2 : 1;
   static_assert(BM % 32 == 0 && BN % 32 == 0, "block tile must be a multiple of 32");
-  // A rows fill whole load slots (compile-time A / B split) unless the A panel is smaller
-  // than one slot (the full-row 32 x H tile: 128 A float4 for 512 threads), then per thread
+  // A rows fill whole load slots (compile-time A / B split); Stager requires it
   static constexpr bool A_SLOTS = (BM * F4_PER_ROW) % THREADS == 0;
 };
 
@@ -128,51 +129,34 @@ __device__ __forceinline__ void static_for(F&& f) {
 // epilogue never stores.  The per-slice path is LOADS x global_load_dwordx4.
 template <class T>
 struct Stager {
+  static_assert(T::A_SLOTS, "A rows fill whole load slots: each slot's operand is known at compile time");
   floatx4 r[T::LOADS];
 
   __device__ __forceinline__ void load(const float* __restrict__ A, int64_t lda, int M, int m0,
                                        const float* __restrict__ B, int64_t ldb, int64_t N,
                                        int64_t n0, int k0, int tid) {
-    if constexpr (T::A_SLOTS) {
-      // Buffer loads off two per-tile resources (scalar: the panel origins A + m0 lda and
-      // B + n0 ldb, so a corpus slab past 4 GB still takes 32-bit offsets), the slice's
-      // k0 in soffset, and a 32-bit per-slot offset (row clamped, 16-B chunk): 2 VALU per
-      // load instead of the 64-bit address arithmetic of a flat load (~60 VALU per slice).
-      const __amdgpu_buffer_rsrc_t ra =
-          __builtin_amdgcn_make_buffer_rsrc((void*)(A + (int64_t)m0 * lda), (short)0, 0x7fffffff, 0x00020000);
-      const __amdgpu_buffer_rsrc_t rb =
-          __builtin_amdgcn_make_buffer_rsrc((void*)(B + n0 * ldb), (short)0, 0x7fffffff, 0x00020000);
-      const int alim = M - 1 - m0;                      // last valid row of the A panel
-      const int blim = (int)min(N - 1 - n0, (int64_t)T::BN - 1);
-      const int a4 = (int)lda * 4, b4 = (int)ldb * 4;
-#pragma unroll
-      for (int i = 0; i < T::LOADS; ++i) {
-        const int f = tid + i * T::THREADS;
-        if (T::PARTIAL && i == T::LOADS - 1 && f >= T::TOTAL_F4) break;
-        const int row = f / T::F4_PER_ROW, ch = f % T::F4_PER_ROW;
-        if (i < T::BM * T::F4_PER_ROW / T::THREADS)
-          r[i] = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                 ra, min(row, alim) * a4 + ch * 16, k0 * 4, 0));
-        else
-          r[i] = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                 rb, min(row - T::BM, blim) * b4 + ch * 16, k0 * 4, T::NTB ? 2 : 0));
-      }
-      return;
-    }
+    // Buffer loads off two per-tile resources (scalar: the panel origins A + m0 lda and
+    // B + n0 ldb, so a corpus slab past 4 GB still takes 32-bit offsets), the slice's
+    // k0 in soffset, and a 32-bit per-slot offset (row clamped, 16-B chunk): 2 VALU per
+    // load instead of the 64-bit address arithmetic of a flat load (~60 VALU per slice).
+    const __amdgpu_buffer_rsrc_t ra =
+        __builtin_amdgcn_make_buffer_rsrc((void*)(A + (int64_t)m0 * lda), (short)0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rb =
+        __builtin_amdgcn_make_buffer_rsrc((void*)(B + n0 * ldb), (short)0, 0x7fffffff, 0x00020000);
+    const int alim = M - 1 - m0;                      // last valid row of the A panel
+    const int blim = (int)min(N - 1 - n0, (int64_t)T::BN - 1);
+    const int a4 = (int)lda * 4, b4 = (int)ldb * 4;
 #pragma unroll
     for (int i = 0; i < T::LOADS; ++i) {
       const int f = tid + i * T::THREADS;
       if (T::PARTIAL && i == T::LOADS - 1 && f >= T::TOTAL_F4) break;
       const int row = f / T::F4_PER_ROW, ch = f % T::F4_PER_ROW;
-      const float* p;
-      const bool a_row = T::A_SLOTS ? i < T::BM * T::F4_PER_ROW / T::THREADS  // compile-time: A rows first
-                                    : f < T::BM * T::F4_PER_ROW;
-      if (a_row) {
-        p = A + (int64_t)min(m0 + row, M - 1) * lda;
-      } else {
-        p = B + min(n0 + (int64_t)(row - T::BM), N - 1) * ldb;
-      }
-      r[i] = *reinterpret_cast<const floatx4*>(p + k0 + ch * 4);
+      if (i < T::BM * T::F4_PER_ROW / T::THREADS)
+        r[i] = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(
+                                               ra, min(row, alim) * a4 + ch * 16, k0 * 4, 0));
+      else
+        r[i] = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(
+                                               rb, min(row - T::BM, blim) * b4 + ch * 16, k0 * 4, T::NTB ? 2 : 0));
     }
   }
 
@@ -446,86 +430,6 @@ __device__ __forceinline__ void walk_tiles(float* lds, int n_tiles, const TileOp
       mma_slice<T>(cur, acc, wm, wn, lane);
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
-      st[(d + 1) % D].store(lds + ((j + 1) & 1) * T::STAGE_FLOATS, tid);
-      __syncthreads();
-      if (nkd.mod(j + 1) == 0) {
-        epi(nkd.div(j), acc, cur);
-        zero_acc<T>(acc);
-      }
-    });
-  }
-}
-
-}  // namespace mq
-
-namespace mq {
-
-// walk_tiles with hooks around the operand staging (D >= 2), for GEMMs that transform an
-// operand between its global load and its LDS write (LayerNorm on load, encoder.hip):
-//   hk.issue(s, IC<d>)      before the loads of slice s (unclamped; s >= S: the re-read
-//                           past the end) into register stage d
-//   hk.prepare(s)           at the store phase of the iteration that fetched slice s, before
-//                           that iteration's barrier (per-tile state into LDS: read by
-//                           xform from the next iteration on)
-//   hk.stage_in(s)          at the top of the iteration that stores slice s (before its
-//                           MFMAs: per-slice state read from LDS under them)
-//   hk.xform(st, s, IC<d>)  on stage d's registers just before they are written to LDS
-// Otherwise the slice schedule is walk_tiles' (same loads, MFMAs, barriers).
-template <class T, int D = T::PF, class Coords, class Epi, class Hooks>
-__device__ __forceinline__ void walk_tiles_hooked(float* lds, int n_tiles, const TileOperands& op,
-                                                  Coords coords, Epi epi, Hooks& hk) {
-  static_assert(D >= 2, "the hooks need the slice's loads one iteration before its store");
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave / T::WAVES_N, wn = wave % T::WAVES_N;
-  const int nk = op.K / T::BK;
-  const int S = n_tiles * nk;
-  if (S == 0) return;
-  const FastDiv nkd(nk);
-  auto fetch = [&](Stager<T>& st, int j) {
-    const int i = nkd.div(j), kt = j - i * nk;
-    int m0;
-    int64_t n0;
-    coords(i, m0, n0);
-    // tile origins are workgroup-uniform: keep them (and the buffer descriptors built from
-    // them) scalar whatever the hooks' per-thread code does to the uniformity analysis
-    m0 = __builtin_amdgcn_readfirstlane(m0);
-    n0 = (int64_t)__builtin_amdgcn_readfirstlane((int)n0);
-    st.load(op.A, op.lda, op.M, m0, op.B, op.ldb, op.N, n0, kt * T::BK, tid);
-  };
-  floatx16 acc[T::TM][T::TN];
-  Stager<T> st[D];
-  static_for<D>([&](auto dc) {
-    constexpr int d = decltype(dc)::value;
-    hk.issue(d, dc);
-    fetch(st[d], d < S ? d : S - 1);
-  });
-  static_for<D>([&](auto dc) { hk.prepare(decltype(dc)::value); });
-  __syncthreads();
-  hk.stage_in(0);
-  hk.xform(st[0], 0, IC<0>{});
-  st[0].store(lds, tid);
-  zero_acc<T>(acc);
-  __syncthreads();
-  for (int j0 = 0; j0 < S; j0 += D) {
-    bool done = false;
-    static_for<D>([&](auto dc) {
-      constexpr int d = decltype(dc)::value;
-      const int j = j0 + d;
-      if (done || j >= S) {
-        done = true;
-        return;
-      }
-      hk.issue(j + D, dc);
-      fetch(st[d], min(j + D, S - 1));
-      hk.stage_in(j + 1);
-      __builtin_amdgcn_sched_barrier(0);
-      float* cur = lds + (j & 1) * T::STAGE_FLOATS;
-      __builtin_amdgcn_s_setprio(1);
-      mma_slice<T>(cur, acc, wm, wn, lane);
-      __builtin_amdgcn_s_setprio(0);
-      __builtin_amdgcn_sched_barrier(0);
-      hk.prepare(j + D);
-      hk.xform(st[(d + 1) % D], j + 1, IC<(d + 1) % D>{});
       st[(d + 1) % D].store(lds + ((j + 1) & 1) * T::STAGE_FLOATS, tid);
       __syncthreads();
       if (nkd.mod(j + 1) == 0) {

@@ -26,10 +26,11 @@ MQ_MASK_SET, MQ_MASK_AND, MQ_MASK_OR, MQ_MASK_CLEAR = 0, 1, 2, 3
 MQ_CONTAINS_MAX_BYTES = 256      # longest mq_mask_contains pattern (UTF-8 bytes)
 MQ_CONTAINS_SPAN_BYTES = 16384   # text bytes one workgroup of the scan owns
 MQ_LEX_MAX_TERMS = 128           # most distinct query terms one mq_lex_df / mq_lex_topk call takes
-# mq_encoder_set_option ids (include/mq.h)
+# mq_encoder_set_option ids (include/mq.h; 3, 5 and 7: retired, never reuse)
 MQ_ENC_OPT_ROWS_MAX, MQ_ENC_OPT_ROWS_SPLITS, MQ_ENC_OPT_SPLITK_MAX = 0, 1, 2
-MQ_ENC_OPT_LN_ROWS_PER_WAVE, MQ_ENC_OPT_FUSE_ATTN_OPROJ, MQ_ENC_OPT_FUSED_LN = 3, 4, 5
-MQ_ENC_OPT_SPLITK_TILES, MQ_ENC_OPT_LN_ON_LOAD, MQ_ENC_OPT_RESIDENT_LAYERS = 6, 7, 8
+MQ_ENC_OPT_FUSE_ATTN_OPROJ = 4
+MQ_ENC_OPT_SPLITK_TILES = 6
+MQ_ENC_OPT_RESIDENT_LAYERS = 8
 MQ_ENC_OPT_X6_PRESPLIT = 9
 MQ_ENC_OPT_ROWS_PLANES = 10
 MQ_ENC_OPT_LN_FOLD = 11

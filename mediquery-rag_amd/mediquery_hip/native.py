@@ -304,9 +304,8 @@ class Encoder:
         _lib.call("mq_encoder_set_graphs", self._h, int(bool(enabled)))
 
     OPTIONS = {"rows_max": _lib.MQ_ENC_OPT_ROWS_MAX, "rows_splits": _lib.MQ_ENC_OPT_ROWS_SPLITS,
-               "splitk_max": _lib.MQ_ENC_OPT_SPLITK_MAX, "ln_rows_per_wave": _lib.MQ_ENC_OPT_LN_ROWS_PER_WAVE,
-               "fuse_attn_oproj": _lib.MQ_ENC_OPT_FUSE_ATTN_OPROJ, "fused_ln": _lib.MQ_ENC_OPT_FUSED_LN,
-               "splitk_tiles": _lib.MQ_ENC_OPT_SPLITK_TILES, "ln_on_load": _lib.MQ_ENC_OPT_LN_ON_LOAD,
+               "splitk_max": _lib.MQ_ENC_OPT_SPLITK_MAX, "fuse_attn_oproj": _lib.MQ_ENC_OPT_FUSE_ATTN_OPROJ,
+               "splitk_tiles": _lib.MQ_ENC_OPT_SPLITK_TILES,
                "resident_layers": _lib.MQ_ENC_OPT_RESIDENT_LAYERS, "x6_presplit": _lib.MQ_ENC_OPT_X6_PRESPLIT,
                "rows_planes": _lib.MQ_ENC_OPT_ROWS_PLANES, "ln_fold": _lib.MQ_ENC_OPT_LN_FOLD,
                "cls_kfree": _lib.MQ_ENC_OPT_CLS_KFREE, "qkv_attn": _lib.MQ_ENC_OPT_QKV_ATTN,
@@ -314,7 +313,7 @@ class Encoder:
 
     def set_option(self, name, value):
         """Tuning option of the forward (mq_encoder_set_option): rows_max, rows_splits,
-        splitk_max, ln_rows_per_wave, fuse_attn_oproj, fused_ln, splitk_tiles, ln_on_load,
+        splitk_max, fuse_attn_oproj, splitk_tiles,
         resident_layers (0..1024, default 8: the few-row forward loads layers below this
         index with the default cache policy and later layers non-temporally, so the first
         layers' weights stay in MALL between single queries; outputs are bit-identical),

@@ -119,7 +119,8 @@ def mean(v):
 EXACT_GEMM = r"gemm_nt_kernel<mq::F32Tile<\d+, \d+, \d+, \d+, false, \d+, false(, \d+)?(, (true|false))?>, "
 # the split-f32 GEMM on pre-split weights (gemm_x6p.hip), its epilogue id captured
 X6P_GEMM = r"gemm_x6p_kernel<mq::X6pTile<[^>]*>, (\d)>"
-# ... then gemm_nt_kernel's LN_IN argument (r4: LayerNorm on load, false by default)
+# ... then, in profiles of builds up to 8d748c3, gemm_nt_kernel's LN_IN argument (r4: LayerNorm
+# on load, since removed)
 LN_ARG = r"(, (true|false))?>"
 # bench.py kernel class -> kernel-name regex (the encoder GEMM classes are resolved per
 # dispatch by classify())
