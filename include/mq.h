@@ -284,6 +284,50 @@ int mq_lex_topk(const uint16_t* tokens, int64_t n_tokens, const int64_t* offsets
                 const uint32_t* keys, const float* w, int n_terms, float c0, float c1,
                 const uint32_t* bits, int k, float* out_scores, int64_t* out_ids, int io_on_device,
                 void* scratch, void* stream);
+/* The same for a batch: one walk of the token blob serves a group of queries, so nq queries
+ * cost about nq / MQ_LEX_BATCH_GROUP scans instead of nq.  Nothing about the definition
+ * changes: row j of mq_lex_topk_batch equals, bit for bit in scores and ids, what mq_lex_topk
+ * returns for query j's arguments, whatever else the batch holds and wherever query j stands
+ * in it, and mq_lex_df_batch's df[i] equals mq_lex_df's for keys[i].
+ *   mq_lex_df_batch    keys: HOST, n_keys >= 1 distinct keys (any number: the call runs as many
+ *                      passes as it needs and synchronises once at the end); df: HOST [n_keys].
+ *                      n == 0: every df is 0.
+ *   mq_lex_topk_batch  term_start: HOST int64 [nq + 1], non-decreasing from 0; query j's terms
+ *                      are keys / w [term_start[j], term_start[j + 1]) (HOST arrays of
+ *                      term_start[nq] entries), 0 .. MQ_LEX_MAX_TERMS of them, distinct within
+ *                      the query (different queries may share keys); a query of 0 terms returns
+ *                      padding only.  c0, c1, bits and k are shared by the batch.  The score of
+ *                      a row is the MQ_LEX_NORM / MQ_LEX_TERM sequence over the query's terms
+ *                      with tf > 0 in the query's own slot order.  out_scores / out_ids [nq, k],
+ *                      both device (io_on_device = 1, asynchronous on `stream` once the packed
+ *                      tables are copied) or both host (synchronous).  nq == 0 is a no-op,
+ *                      n == 0 gives padding only.
+ *   scratch            device, mq_lex_batch_scratch_bytes(n, nq, total_terms, k) bytes
+ *                      (total_terms = term_start[nq], or n_keys with nq = 0 and k = 1 for the df
+ *                      call), 16-byte aligned, not an output.  The size is non-decreasing in
+ *                      every argument and bounded in nq and total_terms (the per-workgroup
+ *                      lists are reused from group to group in stream order), so a buffer sized
+ *                      for larger arguments serves smaller ones.  Neither call allocates or
+ *                      frees device memory: the merged key tables, per-query slot lists and
+ *                      weights are packed on the host and copied into scratch by the call.
+ * lex_batch_kernel (K15): the host cuts the batch, in order, into groups of at most
+ * MQ_LEX_BATCH_GROUP queries whose keys' union has at most MQ_LEX_BATCH_UNION entries; per group
+ * one scan walks the blob as K14 does, counts into tf[row][union slot] (u32, LDS) through a hash
+ * of the union that is at most half full, and wave w of a workgroup scores queries w, w + 4, ...
+ * of the group from those counts, one register-resident sorted list a query; the workgroups'
+ * lists [lists, group, k] go through mq_topk_merge_device into the group's output rows.  The df
+ * pass is the same walk over MQ_LEX_BATCH_UNION keys a pass.  Every argument check (sizes, ngram,
+ * n_keys, term_start, the per-query term count, distinct keys, k, NULL pointers, alignment,
+ * scratch not an output) comes before any HIP call and names the offending value. */
+#define MQ_LEX_BATCH_GROUP 16
+#define MQ_LEX_BATCH_UNION 512
+int64_t mq_lex_batch_scratch_bytes(int64_t n, int64_t nq, int64_t total_terms, int k);
+int mq_lex_df_batch(const uint16_t* tokens, int64_t n_tokens, const int64_t* offsets, int64_t n, int ngram,
+                    const uint32_t* keys, int64_t n_keys, int64_t* df, void* scratch, void* stream);
+int mq_lex_topk_batch(const uint16_t* tokens, int64_t n_tokens, const int64_t* offsets, int64_t n, int ngram,
+                      int64_t nq, const int64_t* term_start, const uint32_t* keys, const float* w, float c0,
+                      float c1, const uint32_t* bits, int k, float* out_scores, int64_t* out_ids,
+                      int io_on_device, void* scratch, void* stream);
 
 /* Maximal marginal relevance (LangChain's maximal_marginal_relevance, the selection behind
  * VectorStore.max_marginal_relevance_search): from each query's candidate list pick k rows

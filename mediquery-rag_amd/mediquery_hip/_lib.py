@@ -26,6 +26,8 @@ MQ_MASK_SET, MQ_MASK_AND, MQ_MASK_OR, MQ_MASK_CLEAR = 0, 1, 2, 3
 MQ_CONTAINS_MAX_BYTES = 256      # longest mq_mask_contains pattern (UTF-8 bytes)
 MQ_CONTAINS_SPAN_BYTES = 16384   # text bytes one workgroup of the scan owns
 MQ_LEX_MAX_TERMS = 128           # most distinct query terms one mq_lex_df / mq_lex_topk call takes
+MQ_LEX_BATCH_GROUP = 16          # most queries one scan of mq_lex_topk_batch serves
+MQ_LEX_BATCH_UNION = 512         # most distinct keys of such a group / of one mq_lex_df_batch pass
 # mq_encoder_set_option ids (include/mq.h; 3, 5 and 7: retired, never reuse)
 MQ_ENC_OPT_ROWS_MAX, MQ_ENC_OPT_ROWS_SPLITS, MQ_ENC_OPT_SPLITK_MAX = 0, 1, 2
 MQ_ENC_OPT_FUSE_ATTN_OPROJ = 4
@@ -103,6 +105,10 @@ SIGNATURES = {
     "mq_lex_df": (_I, [_P, _I64, _P, _I64, _I, _P, _I, _P, _P, _P]),
     "mq_lex_topk": (_I, [_P, _I64, _P, _I64, _I, _P, _P, _I, ctypes.c_float, ctypes.c_float, _P, _I, _P, _P, _I,
                          _P, _P]),
+    "mq_lex_batch_scratch_bytes": (_I64, [_I64, _I64, _I64, _I]),
+    "mq_lex_df_batch": (_I, [_P, _I64, _P, _I64, _I, _P, _I64, _P, _P, _P]),
+    "mq_lex_topk_batch": (_I, [_P, _I64, _P, _I64, _I, _I64, _P, _P, _P, ctypes.c_float, ctypes.c_float, _P, _I,
+                               _P, _P, _I, _P, _P]),
     "mq_index_search_masked": (_I, [_P, _P, _I, _P, _P, _P, _I, _P]),
     "mq_index_search_masked_batch": (_I, [_P, _P, _I64, _I, _P, _P, _P, _I, _P]),
     "mq_index_masked_gathers": (_I, [_P, ctypes.POINTER(_I64)]),

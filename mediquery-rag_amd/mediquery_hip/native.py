@@ -545,6 +545,109 @@ def lex_topk(tokens, offsets, ngram, keys, w, c0, c1, k, bits=None, scratch=None
     return s, i
 
 
+def lex_batch_scratch_bytes(n, nq, total_terms, k=_lib.MQ_MAX_K):
+    """Bytes of device scratch mq_lex_topk_batch wants for n rows, nq queries of total_terms
+    terms in all and a top-k of k (mq_lex_df_batch: nq = 0, total_terms = its keys, k = 1);
+    non-decreasing in every argument and bounded in nq and total_terms."""
+    return int(_lib.lib().mq_lex_batch_scratch_bytes(int(n), int(nq), int(total_terms), int(k)))
+
+
+def _check_lex_mirror(tokens, offsets, ngram):
+    """The device checks of the token mirror shared by the batch calls -> n."""
+    import torch
+    if not (getattr(tokens, "is_cuda", False) and tokens.dtype == torch.uint16 and tokens.is_contiguous()
+            and tokens.dim() == 1):
+        raise ValueError("tokens must be a contiguous 1-d uint16 device tensor")
+    if tokens.numel() and tokens.data_ptr() % 16:
+        raise ValueError("tokens must start at a 16-byte aligned address")
+    if not (getattr(offsets, "is_cuda", False) and offsets.dtype == torch.int64 and offsets.is_contiguous()
+            and offsets.numel() >= 1 and offsets.device == tokens.device):
+        raise ValueError("offsets must be a contiguous int64 tensor of n + 1 elements on the tokens' device")
+    if ngram not in (1, 2):
+        raise ValueError("ngram must be 1 or 2 (got %r)" % (ngram,))
+    return offsets.numel() - 1
+
+
+def _batch_scratch(scratch, need, device):
+    import torch
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=device)
+    if not (getattr(scratch, "is_cuda", False) and scratch.is_contiguous() and scratch.device == device
+            and scratch.numel() * scratch.element_size() >= need and scratch.data_ptr() % 16 == 0):
+        raise ValueError("scratch must be a contiguous 16-byte aligned tensor of >= %d bytes on the tokens' device"
+                         % need)
+    return scratch
+
+
+def lex_df_batch(tokens, offsets, ngram, keys, scratch=None, stream=None):
+    """Document frequencies int64 [n_keys] of any number (>= 1) of distinct uint32 term keys
+    (host) over the token mirror (include/mq.h mq_lex_df_batch): equal to lex_df's, in as many
+    passes of MQ_LEX_BATCH_UNION keys as it takes and one synchronise.  scratch:
+    lex_batch_scratch_bytes(n, 0, n_keys, 1) bytes (None: a torch.empty of that size)."""
+    n = _check_lex_mirror(tokens, offsets, ngram)
+    keys = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1)
+    if keys.size < 1:
+        raise ValueError("a call takes at least 1 key (got 0)")
+    if np.unique(keys).size != keys.size:
+        raise ValueError("keys must be distinct")
+    df = np.zeros(keys.size, dtype=np.int64)
+    with _lib.device_scope(tokens.device.index):
+        scratch = _batch_scratch(scratch, lex_batch_scratch_bytes(n, 0, keys.size, 1), tokens.device)
+        _lib.call("mq_lex_df_batch", _lib.ptr(tokens) if tokens.numel() else None, tokens.numel(),
+                  _lib.ptr(offsets), n, int(ngram), _lib.ptr(keys), keys.size, _lib.ptr(df), _lib.ptr(scratch),
+                  _lib.stream_handle(stream))
+    return df
+
+
+def lex_topk_batch(tokens, offsets, ngram, plans, c0, c1, k, bits=None, scratch=None, stream=None, out=None):
+    """BM25 top-k of a batch of queries in one call (include/mq.h mq_lex_topk_batch): plans a
+    list of (keys, w), each query's 0..MQ_LEX_MAX_TERMS distinct term keys and their fp32 weights
+    (host); c0, c1, bits and k shared.  -> (scores f32 [nq, k], ids int64 [nq, k]) device tensors
+    (`out`: a pair to write into); row j is bit for bit lex_topk's result for plans[j].
+    Asynchronous on `stream` (or the device's current stream) once the tables are copied."""
+    import torch
+    k = int(k)
+    if not 1 <= k <= _lib.MQ_MAX_K:
+        raise ValueError("k must be in [1, %d] (got %d)" % (_lib.MQ_MAX_K, k))
+    n = _check_lex_mirror(tokens, offsets, ngram)
+    nq = len(plans)
+    term_start = np.zeros(nq + 1, dtype=np.int64)
+    all_keys, all_w = [], []
+    for j, (keys, w) in enumerate(plans):
+        keys = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1)
+        w = np.ascontiguousarray(w, dtype=np.float32).reshape(-1)
+        if keys.size > _lib.MQ_LEX_MAX_TERMS:
+            raise ValueError("a query takes 0..%d terms (query %d has %d)" % (_lib.MQ_LEX_MAX_TERMS, j, keys.size))
+        if np.unique(keys).size != keys.size:
+            raise ValueError("keys must be distinct within a query (query %d)" % j)
+        if w.size != keys.size:
+            raise ValueError("query %d: %d keys, %d weights" % (j, keys.size, w.size))
+        term_start[j + 1] = term_start[j] + keys.size
+        all_keys.append(keys)
+        all_w.append(w)
+    keys = np.concatenate(all_keys) if all_keys else np.zeros(0, np.uint32)
+    w = np.concatenate(all_w) if all_w else np.zeros(0, np.float32)
+    if bits is not None:
+        check_mask_words(bits, n, tokens.device.index)
+    with _lib.device_scope(tokens.device.index):
+        if out is None:
+            out = (torch.empty((nq, k), dtype=torch.float32, device=tokens.device),
+                   torch.empty((nq, k), dtype=torch.int64, device=tokens.device))
+        s, i = out
+        if not (s.is_cuda and i.is_cuda and s.device == tokens.device and i.device == tokens.device
+                and s.dtype == torch.float32 and i.dtype == torch.int64 and s.numel() >= nq * k
+                and i.numel() >= nq * k and s.is_contiguous() and i.is_contiguous()):
+            raise ValueError("out must be (float32 [nq, k], int64 [nq, k]) contiguous tensors on the tokens' device")
+        if nq == 0:
+            return s, i
+        scratch = _batch_scratch(scratch, lex_batch_scratch_bytes(n, nq, keys.size, k), tokens.device)
+        _lib.call("mq_lex_topk_batch", _lib.ptr(tokens) if tokens.numel() else None, tokens.numel(),
+                  _lib.ptr(offsets), n, int(ngram), nq, _lib.ptr(term_start), _lib.ptr(keys), _lib.ptr(w),
+                  ctypes.c_float(float(c0)), ctypes.c_float(float(c1)), _lib.ptr(bits), k, _lib.ptr(s), _lib.ptr(i), 1,
+                  _lib.ptr(scratch), _lib.stream_handle(stream))
+    return s, i
+
+
 def mask_combine(dst, src, mode, stream=None):
     """dst (mode)= src (None: all ones; MQ_MASK_CLEAR: zeros) on the device."""
     check_mask_words(dst, 0)

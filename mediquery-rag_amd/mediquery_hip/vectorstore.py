@@ -25,7 +25,11 @@ Lexical and hybrid retrieval (LangChain's `BM25Retriever` and `EnsembleRetriever
 mq_lex_df / mq_lex_topk; the definition is in include/mq.h), `hybrid_search*` fuses the dense
 and the lexical top fetch_k by weighted reciprocal rank (`rrf_fuse`, on the host), and
 `as_retriever(search_type="lexical" | "hybrid")` wraps them.  Both take `filter` and
-`where_document`.  Nothing of it is persisted: the mirror is derived from the documents.
+`where_document`.  Nothing of it is persisted: the mirror is derived from the documents.  The
+`*_batch` forms of two or more queries tokenise the batch once, fetch the document frequencies
+the cache lacks with one mq_lex_df_batch and rank all queries with one mq_lex_topk_batch (one
+scan of the mirror per group of up to 16 queries, one copy of the [nq, k] result); every row
+is bit for bit the single query's, which one query alone still takes.
 
 Persistence: `mq_<collection>.json` (ids, documents, metadatas, and the name of the slab
 file) is the base commit point; a full write (the first write, `delete`, an upsert that
@@ -52,9 +56,14 @@ import numpy as np
 
 from . import _lib
 from .compat import Document, VectorStoreBase
-from .native import (FlatIndex, lex_df, lex_scratch_bytes, lex_topk, mask_combine, mask_contains, mask_eval,
+from .native import (FlatIndex, lex_batch_scratch_bytes, lex_df, lex_df_batch, lex_scratch_bytes, lex_topk,
+                     lex_topk_batch, mask_combine, mask_contains, mask_eval,
                      mask_eval_bits)
 
+# `*_batch` lexical / hybrid calls of at least this many queries take the batched scan
+# (mq_lex_topk_batch); fewer take the single-query path.  Measured at 1M rows (DESIGN.md, K15,
+# "Crossover"): two queries are never slower batched than looped, four or more always faster.
+LEX_BATCH_MIN = 2
 DEFAULT_K = 4  # LangChain VectorStore.similarity_search default; the reference passes k=5
 
 # search arithmetic (`HipChroma(search_precision=...)`): "screen" (default) = exact fp32
@@ -475,10 +484,12 @@ class _TokenMirror:
         self.blob = torch.empty(0, dtype=torch.int16, device=self.dev)
         self.offs = torch.zeros(1, dtype=torch.int64, device=self.dev)
         self.scratch = torch.empty(lex_scratch_bytes(1 << 40, _lib.MQ_MAX_K), dtype=torch.uint8, device=self.dev)
+        self.batch_scratch = None  # mq_lex_df_batch / mq_lex_topk_batch: allocated at the first batch
 
     def nbytes(self):
         """HBM the mirror holds (allocated capacity, scratch included)."""
-        return self.blob.numel() * 2 + self.offs.numel() * 8 + self.scratch.numel()
+        return (self.blob.numel() * 2 + self.offs.numel() * 8 + self.scratch.numel()
+                + (0 if self.batch_scratch is None else self.batch_scratch.numel()))
 
     def extend(self, texts):
         """Append rows `texts` (the store's rows n .. n + len(texts)); drops the df cache."""
@@ -527,6 +538,46 @@ class _TokenMirror:
         keys, w, c0, c1 = plan
         s, i = lex_topk(tokens, offs, self.ngram, keys, w, c0, c1, k, bits=bits, scratch=self.scratch)
         return s.cpu().numpy(), i.cpu().numpy()
+
+    def plan_batch(self, queries, k1, b):
+        """`plan` for a batch -> one (keys, w, c0, c1) or None per query, each exactly what
+        `plan` returns for it: one tokenizer call, and one mq_lex_df_batch for the batch's
+        distinct keys the df cache lacks."""
+        queries = list(queries)
+        flat, lens = body_tokens(self.tokenizer, queries)
+        if self.sum_dl == 0:
+            return [None] * len(queries)
+        ends = np.cumsum(lens)
+        split = [np.unique(term_keys(flat[e - ln:e], self.ngram), return_counts=True) for e, ln in zip(ends, lens)]
+        seen = np.unique(np.concatenate([keys for keys, _ in split])) if split else np.zeros(0, np.uint32)
+        miss = [int(x) for x in seen if int(x) not in self.df]
+        if miss:
+            tokens, offs = self._views()
+            self._batch_room(0, len(miss), 1)
+            got = lex_df_batch(tokens, offs, self.ngram, np.array(miss, np.uint32), scratch=self.batch_scratch)
+            self.df.update(zip(miss, got.tolist()))
+        avgdl = self.sum_dl / self.n
+        return [bm25_plan(keys, qf, np.array([self.df[int(x)] for x in keys], dtype=np.int64), self.n, avgdl, k1, b)
+                if keys.size else None for keys, qf in split]
+
+    def topk_batch(self, plans, k, bits):
+        """-> (scores f32 [nq, k], rows int64 [nq, k]) on the host for plans (none None, of one
+        `plan_batch`, so c0 and c1 are shared): one mq_lex_topk_batch, the result copied once."""
+        tokens, offs = self._views()
+        c0, c1 = plans[0][2], plans[0][3]
+        assert all(p[2] == c0 and p[3] == c1 for p in plans)
+        self._batch_room(len(plans), sum(len(p[0]) for p in plans), k)
+        s, i = lex_topk_batch(tokens, offs, self.ngram, [(p[0], p[1]) for p in plans], c0, c1, k, bits=bits,
+                              scratch=self.batch_scratch)
+        return s.cpu().numpy(), i.cpu().numpy()
+
+    def _batch_room(self, nq, total_terms, k):
+        """The batch calls' scratch: grows on demand (to the size for any row count) and is kept."""
+        import torch
+        need = lex_batch_scratch_bytes(1 << 40, nq, total_terms, k)
+        if self.batch_scratch is None or self.batch_scratch.numel() < need:
+            self.batch_scratch = None  # release before growing
+            self.batch_scratch = torch.empty(need, dtype=torch.uint8, device=self.dev)
 
 
 class _LexicalRetriever:
@@ -1168,6 +1219,21 @@ class HipChroma(VectorStoreBase):
         s, i = mir.topk(plan, int(k), bits)
         return [(int(r), float(x)) for r, x in zip(i, s) if r >= 0]
 
+    def _lex_rows_batch(self, mir, queries, k, bits):
+        """`_lex_rows` of every query.  Two or more queries take the batch path: one plan_batch
+        (one tokenizer call, one df call) and one topk_batch (one scan per group of queries, one
+        copy of the result); a query without terms gets [].  One query keeps the single path."""
+        if len(queries) < LEX_BATCH_MIN or k <= 0:
+            return [self._lex_rows(mir, q, k, bits) for q in queries]
+        plans = mir.plan_batch(queries, *self._bm25)
+        live = [j for j, p in enumerate(plans) if p is not None]
+        out = [[] for _ in queries]
+        if live:
+            s, i = mir.topk_batch([plans[j] for j in live], int(k), bits)
+            for j, sj, ij in zip(live, s, i):
+                out[j] = [(int(r), float(x)) for r, x in zip(ij, sj) if r >= 0]
+        return out
+
     def lexical_search_with_score(self, query, k=DEFAULT_K, filter=None, where_document=None, **kwargs):
         """(Document, BM25 score) pairs, best first: the rows holding at least one of the query's
         terms, ranked on the device over the token mirror (include/mq.h, "Lexical retrieval")."""
@@ -1185,10 +1251,12 @@ class HipChroma(VectorStoreBase):
         if k == 0 or not queries:
             return [[] for _ in queries]
         mir = self._lex()
-        return [[(self._doc(r), x) for r, x in self._lex_rows(mir, q, k, bits)] for q in queries]
+        return [[(self._doc(r), x) for r, x in rows] for rows in self._lex_rows_batch(mir, queries, k, bits)]
 
     def lexical_search_batch(self, queries, k=DEFAULT_K, filter=None, where_document=None):
-        """Many queries: the mask is built once, the scans are looped (one launch a query)."""
+        """Many queries: the mask is built once and two or more queries are ranked by the batch
+        path (mq_lex_df_batch / mq_lex_topk_batch: one scan of the token mirror per group of up
+        to 16 queries instead of one per query); each result is the single query's exactly."""
         return [[d for d, _ in hits]
                 for hits in self.lexical_search_batch_with_score(queries, k, filter, where_document)]
 
@@ -1218,8 +1286,8 @@ class HipChroma(VectorStoreBase):
         _, dense = self._index.search(q, fk) if bits is None else self._index.search_masked(q, fk, bits)
         mir = self._lex()
         out = []
-        for query, drow in zip(queries, dense):
-            lex = [r for r, _ in self._lex_rows(mir, query, fk, bits)]
+        for lrow, drow in zip(self._lex_rows_batch(mir, queries, fk, bits), dense):
+            lex = [r for r, _ in lrow]
             fused = rrf_fuse([int(r) for r in drow if r >= 0], lex, weights, c, k)
             out.append([(self._doc(r), x) for r, x in fused])
         return out
@@ -1238,7 +1306,8 @@ class HipChroma(VectorStoreBase):
 
     def hybrid_search_batch(self, queries, k=DEFAULT_K, fetch_k=20, weights=(0.5, 0.5), c=60, filter=None,
                             where_document=None):
-        """Many queries: one encoder batch, one dense search, looped lexical scans."""
+        """Many queries: one encoder batch, one dense search, one batched lexical call (as
+        `lexical_search_batch`); the fusion stays on the host."""
         return [[d for d, _ in hits]
                 for hits in self._hybrid(queries, k, fetch_k, weights, c, filter, where_document)]
 
