@@ -376,6 +376,58 @@ int mq_index_search_mmr(mq_index* ix, const float* queries, int64_t nq, int k, i
                         float lambda, const uint32_t* bits, float* out_scores, int64_t* out_ids,
                         int io_on_device, void* stream);
 
+/* Grouped search (K16; LangChain's ParentDocumentRetriever / MultiVectorRetriever: embed
+ * small child chunks, return the distinct parents): the top-k GROUPS of a row-to-group map,
+ * each by its best row, over the whole index - not the distinct groups among a top-k of rows.
+ * Inputs: the index rows; a device int32 codes[n], the group code of each row; n_groups; an
+ * optional device row mask `bits` in the layout of the masked search (NULL: every row); nq
+ * queries; k.
+ * Candidates: row r is a candidate of a query when the mask admits it and
+ * 0 <= codes[r] < n_groups.  Code -1 means the metadata key is absent, and any other code out
+ * of range is treated the same way: such rows are ignored, never read as a group and never
+ * written anywhere (MultiVectorRetriever skips children without its id_key).
+ * Scores: score(q, r) = the exact fp32 dot of the query with the stored, already normalised
+ * row; the query is taken as given, as on mq_index_search's exact path.  A group's score is
+ * the maximum over its candidate rows and its representative the row reaching it, equal
+ * scores going to the lowest row id.  Groups rank by (score desc, representative row id asc).
+ * Output: out_scores / out_ids [nq, k] = (score, representative row id) of the top-k groups,
+ * padded with (-inf, -1) when fewer than k groups have a candidate; an empty index,
+ * n_groups == 0 or an all-zero mask return padding only.  1 <= k <= MQ_MAX_K.
+ * Equivalently: the distinct codes of the full ranking of the candidate rows, in order of
+ * first appearance, with the row that introduced each - what LangChain's collapse of a
+ * top-k yields when that k covers every row.
+ *
+ * group_scan_kernel walks the rows as the streaming exact scan does (16 lanes per row, at most
+ * 16 queries per pass, mq_group_scan_blocks(n, CUs) workgroups of 16 lane groups, two rows in
+ * flight per lane group) and raises best[query][code], a uint64 [<= 16][n_groups] table in the
+ * scratch that the call zeroes on the stream first, by an atomic maximum of the key
+ * (orderable score bits << 32) | (0xFFFFFFFF - row); group_select_kernel takes each query's
+ * top-k keys in up to 64 workgroup lists that mq_topk_merge_device merges.  More than 16
+ * queries run as successive passes that reuse the table in stream order.  The maximum does
+ * not depend on the order the rows arrive in: repeated calls return the same bits.
+ *
+ * queries [nq, dim] and the outputs are all host (io_on_device = 0: staged through the scratch,
+ * the call synchronises) or all device (asynchronous on `stream`); codes, bits and scratch are
+ * device memory of the index's GPU.  Checked before any HIP call, each with a message naming
+ * the offending value: k, nq, n_groups >= 0, dim % 64 == 0 and dim <= 1024, n < 2^31 (the
+ * slab is fp32: no other index dtype exists), non-NULL buffers, scratch 16-byte aligned, at
+ * least mq_group_scratch_bytes(n_groups, nq, k) bytes and overlapping neither output.  The
+ * call allocates and frees no device memory, and always runs the full scan: it is the
+ * definition (the store answers most queries from a certified top-64 first).
+ * It reads the slab as it stood when the call began: an mq_index_add / _select / _reset /
+ * _load on the same handle must not run concurrently with it.
+ * mq_group_scratch_bytes is non-decreasing in every argument and bounded in nq (a multiple
+ * of 256; arguments out of range are clamped).  mq_debug_group_check runs the HIP-free checks
+ * alone on a stated index shape (dim, n_rows), for hosts without a GPU to make an index on. */
+int64_t mq_group_scratch_bytes(int64_t n_groups, int64_t nq, int k);
+int mq_group_scan_blocks(int64_t n_rows, int compute_units);
+int mq_index_search_grouped(mq_index* ix, const float* queries, int64_t nq, int k, const int32_t* codes,
+                            int32_t n_groups, const uint32_t* bits, float* out_scores, int64_t* out_ids,
+                            int io_on_device, void* scratch, int64_t scratch_bytes, void* stream);
+int mq_debug_group_check(int dim, int64_t n_rows, const float* queries, int64_t nq, int k, const int32_t* codes,
+                         int32_t n_groups, const float* out_scores, const int64_t* out_ids, const void* scratch,
+                         int64_t scratch_bytes);
+
 /* Persistence: a flat binary slab (header + rows); written files are
  * fsync'ed before the call returns. */
 int mq_index_save(mq_index* ix, const char* path);

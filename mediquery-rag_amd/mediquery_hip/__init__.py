@@ -5,6 +5,8 @@ Drop-in replacements for the reference's retrieval pair:
     langchain_chroma.Chroma                        ->  HipChroma
 and, over what a search returns, LangChain's cross-encoder reranking:
     HuggingFaceCrossEncoder / CrossEncoderReranker ->  HipCrossEncoder / HipReranker
+and its parent-document retrieval over child chunks:
+    langchain.retrievers.ParentDocumentRetriever   ->  HipParentDocumentRetriever
 backed by libmqhip.so (hand-written HIP for gfx950, C ABI in include/mq.h).
 """
 from .config import BertConfig, DMETA_BASE, GELU_ERF, GELU_TANH, POOL_CLS, POOL_MEAN
@@ -14,6 +16,7 @@ from .native import Encoder, FlatIndex, merge_topk_device, merge_topk_host
 from .embeddings import HipBertEmbeddings
 from .vectorstore import HipChroma
 from .cross_encoder import HipCrossEncoder, HipReranker
+from .parent_retriever import HipParentDocumentRetriever, WindowSplitter
 
 # LangChain-compatible aliases for a one-line swap at src/medical_engine.py:25-26
 OllamaEmbeddings = HipBertEmbeddings
@@ -22,4 +25,5 @@ Chroma = HipChroma
 __all__ = ["BertConfig", "DMETA_BASE", "GELU_ERF", "GELU_TANH", "POOL_CLS", "POOL_MEAN",
            "Document", "HAVE_LANGCHAIN", "MQError", "MQ_MAX_K", "device_count", "lib", "Encoder",
            "FlatIndex", "merge_topk_device", "merge_topk_host", "HipBertEmbeddings", "HipChroma",
-           "OllamaEmbeddings", "Chroma", "HipCrossEncoder", "HipReranker"]
+           "OllamaEmbeddings", "Chroma", "HipCrossEncoder", "HipReranker",
+           "HipParentDocumentRetriever", "WindowSplitter"]

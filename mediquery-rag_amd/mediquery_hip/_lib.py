@@ -114,6 +114,10 @@ SIGNATURES = {
     "mq_index_masked_gathers": (_I, [_P, ctypes.POINTER(_I64)]),
     "mq_index_mmr_select": (_I, [_P, _P, _P, _I64, _I, _I, ctypes.c_float, _P, _P, _I, _P]),
     "mq_index_search_mmr": (_I, [_P, _P, _I64, _I, _I, ctypes.c_float, _P, _P, _P, _I, _P]),
+    "mq_group_scratch_bytes": (_I64, [_I64, _I64, _I]),
+    "mq_group_scan_blocks": (_I, [_I64, _I]),
+    "mq_index_search_grouped": (_I, [_P, _P, _I64, _I, _P, ctypes.c_int32, _P, _P, _P, _I, _P, _I64, _P]),
+    "mq_debug_group_check": (_I, [_I, _I64, _P, _I64, _I, _P, ctypes.c_int32, _P, _P, _P, _I64]),
     "mq_topk_merge_host": (_I, [_P, _P, _I, _I64, _I, _I, _P, _P]),
     "mq_topk_merge_device": (_I, [_P, _P, _I, _I64, _I, _I, _P, _P, _P]),
     "mq_encoder_create": (_I, [_I, ctypes.POINTER(BertConfigC), _PP]),

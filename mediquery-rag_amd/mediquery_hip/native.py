@@ -220,6 +220,68 @@ class FlatIndex:
                       _lib.ptr(bits), _lib.ptr(scores), _lib.ptr(ids), 0, _lib.stream_handle(None))
         return scores, ids
 
+    def _group_args(self, codes, n_groups, bits, scratch, nq, k):
+        """The device checks of the grouped calls -> (n_groups, scratch)."""
+        import torch
+        n, n_groups, k = len(self), int(n_groups), int(k)
+        if not 1 <= k <= _lib.MQ_MAX_K:
+            raise ValueError("k must be in [1, %d] (got %d)" % (_lib.MQ_MAX_K, k))
+        if n_groups < 0:
+            raise ValueError("n_groups must be >= 0 (got %d)" % n_groups)
+        if self.dim % 64 or self.dim > 1024:
+            raise ValueError("the grouped scan serves dim %% 64 == 0, dim <= 1024 (got %d)" % self.dim)
+        if not (getattr(codes, "is_cuda", False) and codes.dtype == torch.int32 and codes.is_contiguous()
+                and codes.device.index == int(self.device) and codes.numel() >= n):
+            raise ValueError("codes must be a contiguous int32 tensor of >= %d elements on cuda:%d" % (n, self.device))
+        if bits is not None:
+            self._check_bits(bits)
+        need = group_scratch_bytes(n_groups, nq, k)
+        if scratch is None:
+            scratch = torch.empty(max(need, 256), dtype=torch.uint8, device=codes.device)
+        if not (getattr(scratch, "is_cuda", False) and scratch.is_contiguous()
+                and scratch.device.index == int(self.device)
+                and scratch.numel() * scratch.element_size() >= need and scratch.data_ptr() % 16 == 0):
+            raise ValueError("scratch must be a contiguous 16-byte aligned tensor of >= %d bytes on cuda:%d"
+                             % (need, self.device))
+        return n_groups, scratch
+
+    def search_grouped(self, queries, k, codes, n_groups, bits=None, scratch=None):
+        """Top-k distinct groups (K16, mq_index_search_grouped): codes a device int32 tensor
+        [n] of each row's group code (outside [0, n_groups): the row is ignored), bits a row
+        mask as for search_masked (None = every row), scratch group_scratch_bytes(n_groups,
+        nq, k) device bytes (None: a torch.empty of that size).  -> (scores [nq, k], ids
+        [nq, k]): each group's best score and the row reaching it (ties: the lowest row),
+        groups by (score desc, row asc), padded with (-inf, -1).  Always the full scan."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        with _lib.device_scope(self.device):
+            n_groups, scratch = self._group_args(codes, n_groups, bits, scratch, q.shape[0], k)
+            scores = np.empty((q.shape[0], k), dtype=np.float32)
+            ids = np.empty((q.shape[0], k), dtype=np.int64)
+            _lib.call("mq_index_search_grouped", self._h, _lib.ptr(q), q.shape[0], int(k), _lib.ptr(codes), n_groups,
+                      _lib.ptr(bits), _lib.ptr(scores), _lib.ptr(ids), 0, _lib.ptr(scratch),
+                      scratch.numel() * scratch.element_size(), _lib.stream_handle(None))
+        return scores, ids
+
+    def search_grouped_device(self, queries, k, codes, n_groups, out_scores, out_ids, bits=None, scratch=None,
+                              stream=None):
+        """search_grouped on torch device tensors (queries [nq, dim] f32, out_scores [nq, k]
+        f32, out_ids [nq, k] int64), asynchronous on the given (or current) torch stream."""
+        import torch
+        nq = queries.shape[0]
+        for t, dt, cnt in ((queries, torch.float32, nq * self.dim), (out_scores, torch.float32, nq * int(k)),
+                           (out_ids, torch.int64, nq * int(k))):
+            if not (getattr(t, "is_cuda", False) and t.dtype == dt and t.is_contiguous()
+                    and t.device.index == int(self.device) and t.numel() >= cnt):
+                raise ValueError("queries / out_scores / out_ids must be contiguous float32 / float32 / int64 "
+                                 "tensors of [nq, dim] / [nq, k] / [nq, k] on cuda:%d" % self.device)
+        with _lib.device_scope(self.device):
+            n_groups, scratch = self._group_args(codes, n_groups, bits, scratch, nq, k)
+            if scratch.data_ptr() in (out_scores.data_ptr(), out_ids.data_ptr()):
+                raise ValueError("scratch must not be one of the outputs")
+            _lib.call("mq_index_search_grouped", self._h, _lib.ptr(queries), nq, int(k), _lib.ptr(codes), n_groups,
+                      _lib.ptr(bits), _lib.ptr(out_scores), _lib.ptr(out_ids), 1, _lib.ptr(scratch),
+                      scratch.numel() * scratch.element_size(), _lib.stream_handle(stream))
+
     @property
     def masked_gathers(self):
         """Masked searches the int8 screen did not certify (answered from gathered rows)."""
@@ -234,6 +296,18 @@ class FlatIndex:
     def load_append(self, path):
         """Append a slab file's rows, bit-identical (no re-normalisation)."""
         _lib.call("mq_index_load_append", self._h, str(path).encode())
+
+
+def group_scratch_bytes(n_groups, nq, k=_lib.MQ_MAX_K):
+    """Bytes of device scratch mq_index_search_grouped wants for n_groups groups, nq queries
+    and a top-k of k; non-decreasing in every argument and bounded in nq."""
+    return int(_lib.lib().mq_group_scratch_bytes(int(n_groups), int(nq), int(k)))
+
+
+def group_scan_blocks(n_rows, compute_units):
+    """Workgroups of the grouped scan over n_rows on a GPU of compute_units CUs; each holds 16
+    lane groups, and lane group g walks rows g, g + 16 * blocks, ..., two per iteration."""
+    return int(_lib.lib().mq_group_scan_blocks(int(n_rows), int(compute_units)))
 
 
 def merge_topk_host(scores, ids, k_out):

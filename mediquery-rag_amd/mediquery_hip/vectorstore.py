@@ -31,6 +31,14 @@ the cache lacks with one mq_lex_df_batch and rank all queries with one mq_lex_to
 scan of the mirror per group of up to 16 queries, one copy of the [nq, k] result); every row
 is bit for bit the single query's, which one query alone still takes.
 
+Grouped retrieval (LangChain's `ParentDocumentRetriever` / `MultiVectorRetriever`: small child
+chunks that name their parent in metadata): `similarity_search_grouped*` returns the best child
+of each of the top-k distinct values of a metadata key, over the whole store.  A query is
+answered from the ordinary top-64 when that list certifies the answer (`collapse_candidates`)
+and by the device group scan otherwise (mq_index_search_grouped, the definition: include/mq.h
+"Grouped search"); `as_retriever(search_type="grouped")` wraps it, and
+`parent_retriever.HipParentDocumentRetriever` maps the children back to their parents.
+
 Persistence: `mq_<collection>.json` (ids, documents, metadatas, and the name of the slab
 file) is the base commit point; a full write (the first write, `delete`, an upsert that
 replaces rows, an explicit `persist()`) puts the rows in a fresh `mq_<collection>.<gen>.flat`
@@ -56,8 +64,8 @@ import numpy as np
 
 from . import _lib
 from .compat import Document, VectorStoreBase
-from .native import (FlatIndex, lex_batch_scratch_bytes, lex_df, lex_df_batch, lex_scratch_bytes, lex_topk,
-                     lex_topk_batch, mask_combine, mask_contains, mask_eval,
+from .native import (FlatIndex, group_scratch_bytes, lex_batch_scratch_bytes, lex_df, lex_df_batch,
+                     lex_scratch_bytes, lex_topk, lex_topk_batch, mask_combine, mask_contains, mask_eval,
                      mask_eval_bits)
 
 # `*_batch` lexical / hybrid calls of at least this many queries take the batched scan
@@ -580,9 +588,36 @@ class _TokenMirror:
             self.batch_scratch = torch.empty(need, dtype=torch.uint8, device=self.dev)
 
 
+def collapse_candidates(ids, scores, codes, k):
+    """One query's top list of ROWS (ids / scores as the search returns them: best first by
+    (score desc, row asc), padded with -1) collapsed to its distinct groups, LangChain's way:
+    the first row of each new code, in list order; rows whose code is absent (< 0) are skipped.
+    codes: the host group code of every row.  -> (rows, scores, certified): at most k
+    representative rows with their scores, and whether they are THE top-k groups of the whole
+    candidate set.  They are when the list holds at least k distinct groups - a group absent
+    from a full list has best score <= the list's last score <= every present group's best, and
+    in the (score desc, row asc) order every absent row comes after every listed one - or when
+    the list is shorter than MQ_MAX_K valid entries, because then it holds every candidate."""
+    rows, out, seen, valid = [], [], set(), 0
+    for r, s in zip(ids, scores):
+        r = int(r)
+        if r < 0:
+            continue
+        valid += 1
+        c = int(codes[r])
+        if c < 0 or c in seen:
+            continue
+        seen.add(c)
+        if len(rows) < k:
+            rows.append(r)
+            out.append(float(s))
+    return rows, out, len(seen) >= k or valid < _lib.MQ_MAX_K
+
+
 class _LexicalRetriever:
-    """What `HipChroma.as_retriever(search_type="lexical" | "hybrid")` returns: `invoke` /
-    `get_relevant_documents` call the store's method with the retriever's search_kwargs."""
+    """What `HipChroma.as_retriever(search_type="lexical" | "hybrid" | "grouped")` returns:
+    `invoke` / `get_relevant_documents` call the store's method with the retriever's
+    search_kwargs."""
 
     def __init__(self, store, search_type, search_kwargs):
         self.vectorstore = store
@@ -590,8 +625,8 @@ class _LexicalRetriever:
         self.search_kwargs = dict(search_kwargs or {})
 
     def invoke(self, query, config=None, **kwargs):
-        fn = (self.vectorstore.lexical_search if self.search_type == "lexical"
-              else self.vectorstore.hybrid_search)
+        fn = {"lexical": self.vectorstore.lexical_search, "hybrid": self.vectorstore.hybrid_search,
+              "grouped": self.vectorstore.similarity_search_grouped}[self.search_type]
         return fn(query, **self.search_kwargs)
 
     get_relevant_documents = invoke
@@ -710,6 +745,9 @@ class HipChroma(VectorStoreBase):
         self._lex_ngram = int(lexical_ngram)
         self._bm25 = (float(bm25_k1), float(bm25_b))
         self._lex_mirror = None        # _TokenMirror, built at the first lexical use
+        self.group_scans = 0           # grouped queries the top-64 did not certify (sent to the scan)
+        self._group_scratch = None     # the group scan's device scratch, grown on demand
+        self._group_absent = None      # ((key, codes version), some row lacks the key)
         if search_precision not in SEARCH_PRECISIONS:
             raise ValueError("search_precision must be one of %s, got %r"
                              % (sorted(SEARCH_PRECISIONS), search_precision))
@@ -1173,6 +1211,125 @@ class HipChroma(VectorStoreBase):
         return [[self._doc(r) for r in rows]
                 for rows in self._mmr_rows(q, k, fetch_k, lambda_mult, filter, where_document)]
 
+    # ---- grouped search: the top-k distinct values of a metadata key -------------------------
+    def _group_room(self, n_groups, nq, k):
+        """The group scan's scratch: grows on demand and is kept."""
+        import torch
+        need = group_scratch_bytes(n_groups, nq, k)
+        if self._group_scratch is None or self._group_scratch.numel() < need:
+            self._group_scratch = None  # release before growing
+            with _lib.device_scope(self._device):
+                self._group_scratch = torch.empty(need, dtype=torch.uint8, device=torch.device("cuda", self._device))
+        return self._group_scratch
+
+    def _grouped_rows(self, q, k, group_by, filter=None, where_document=None, force_scan=False):
+        """-> per query [(row, cosine)]: the representative child row of each of the top-k
+        groups of metadata key `group_by`, best first (include/mq.h, "Grouped search").
+        Stage 1, the certificate: the ordinary top min(64, rows) (the masked search when a
+        filter, a where_document clause or rows without the key are in play, its mask ANDed
+        with "has the key") collapsed on the host; `collapse_candidates` says when that is the
+        answer.  Stage 2: the uncertified queries of the batch go to ONE mq_index_search_grouped
+        call (counted in `group_scans`).  search_precision "bf16" is approximate, so its list
+        certifies nothing: it always scans, as `force_scan` does."""
+        if where_document is not None:
+            _check_where_document(where_document)
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self._dim or 1)
+        nothing = [[] for _ in range(len(q))]
+        n = 0 if self._index is None else len(self._index)
+        col = self._cols.cols.get(group_by)
+        if n == 0 or k <= 0 or not len(q) or col is None or not col[1]:
+            return nothing
+        if self._dim % 64 or self._dim > 1024:
+            raise ValueError("grouped search serves stores of dim %% 64 == 0, dim <= 1024 (this store's dim is %d)"
+                             % self._dim)
+        n_groups = len(col[1])
+        if k > _lib.MQ_MAX_K and n_groups > _lib.MQ_MAX_K:
+            raise ValueError("a grouped search returning %d groups (k=%d over %d groups) exceeds the device "
+                             "top-k limit MQ_MAX_K=%d" % (min(k, n_groups), k, n_groups, _lib.MQ_MAX_K))
+        k = min(int(k), n_groups)
+        codes = col[0][:n]
+        import torch
+        dev = torch.device("cuda", self._device)
+        dcodes = self._cols.dev_codes(group_by, dev)
+        bits = None
+        if filter or where_document is not None:
+            _, bits = self._admit(1, filter, where_document)
+        out = [None] * len(q)
+        todo = list(range(len(q)))
+        if not force_scan and self._search_precision != "bf16":
+            key = (group_by, self._cols.ver)
+            if self._group_absent is None or self._group_absent[0] != key:
+                self._group_absent = (key, bool((codes < 0).any()))
+            mask1 = bits
+            if self._group_absent[1]:  # rows without the key would crowd the list: mask them out
+                with _lib.device_scope(self._device):
+                    if bits is None:
+                        mask1 = torch.empty(max(1, (n + 31) // 32), dtype=torch.int32, device=dev)
+                        mask_combine(mask1, None, _lib.MQ_MASK_SET)
+                    else:
+                        mask1 = bits.clone()
+                    lut = np.ones(n_groups + 1, np.uint8)
+                    lut[-1] = 0  # the absent entry
+                    if len(lut) <= 256:
+                        mask_eval_bits(dcodes, lut, mask1, _lib.MQ_MASK_AND)
+                    else:
+                        mask_eval(dcodes, torch.from_numpy(lut).to(dev), mask1, _lib.MQ_MASK_AND)
+            kk = min(_lib.MQ_MAX_K, n)
+            s, i = self._index.search(q, kk) if mask1 is None else self._index.search_masked(q, kk, mask1)
+            todo = []
+            for j in range(len(q)):
+                rows, sc, certified = collapse_candidates(i[j], s[j], codes, k)
+                if certified:
+                    out[j] = list(zip(rows, sc))
+                else:
+                    todo.append(j)
+        if todo:
+            self.group_scans += len(todo)
+            s, i = self._index.search_grouped(q[todo], k, dcodes, n_groups, bits,
+                                              self._group_room(n_groups, len(todo), k))
+            for j, sj, ij in zip(todo, s, i):
+                out[j] = [(int(r), float(c)) for r, c in zip(ij, sj) if r >= 0]
+        return out
+
+    def similarity_search_grouped_by_vector_with_score(self, embedding, k=DEFAULT_K, group_by="doc_id", filter=None,
+                                                       where_document=None, _force_scan=False, **kwargs):
+        """(Document, squared L2 distance) of the best child of each of the top-k distinct
+        `group_by` values, best first: k counts groups, not rows.  Rows without the key are
+        skipped (as LangChain's MultiVectorRetriever skips them); a key no row has returns []."""
+        return [(self._doc(r), max(0.0, 2.0 - 2.0 * c))
+                for r, c in self._grouped_rows(embedding, k, group_by, filter, where_document, _force_scan)[0]]
+
+    def similarity_search_grouped_with_score(self, query, k=DEFAULT_K, group_by="doc_id", filter=None,
+                                             where_document=None, _force_scan=False, **kwargs):
+        if where_document is not None:
+            _check_where_document(where_document)
+        if self._index is None or len(self._index) == 0 or k <= 0:
+            return []
+        return self.similarity_search_grouped_by_vector_with_score(self._embed_query(query), k, group_by, filter,
+                                                                   where_document, _force_scan)
+
+    def similarity_search_grouped(self, query, k=DEFAULT_K, group_by="doc_id", filter=None, where_document=None,
+                                  _force_scan=False, **kwargs):
+        return [d for d, _ in self.similarity_search_grouped_with_score(query, k, group_by, filter, where_document,
+                                                                        _force_scan)]
+
+    def similarity_search_grouped_batch(self, queries, k=DEFAULT_K, group_by="doc_id", filter=None,
+                                        where_document=None, _force_scan=False):
+        """Many queries: one encoder batch, one device search for the certificates, and one
+        group scan call for the queries it leaves uncertified."""
+        if where_document is not None:
+            _check_where_document(where_document)
+        queries = list(queries)
+        n = 0 if self._index is None else len(self._index)
+        if n == 0 or not queries or k <= 0:
+            return [[] for _ in queries]
+        if hasattr(self._embedding_function, "embed_array"):
+            q = self._embedding_function.embed_array(queries)
+        else:
+            q = np.asarray(self._embedding_function.embed_documents(queries), np.float32)
+        return [[self._doc(r) for r, _ in rows]
+                for rows in self._grouped_rows(q, k, group_by, filter, where_document, _force_scan)]
+
     # ---- lexical (BM25) and hybrid (reciprocal rank fusion) retrieval ----------------------
     def _lex_tok(self):
         tok = self._lex_tokenizer
@@ -1312,9 +1469,10 @@ class HipChroma(VectorStoreBase):
                 for hits in self._hybrid(queries, k, fetch_k, weights, c, filter, where_document)]
 
     def as_retriever(self, **kwargs):
-        """search_type "lexical" / "hybrid": a retriever over `lexical_search` / `hybrid_search`
-        with search_kwargs passed on; every other type is the base class's."""
-        if kwargs.get("search_type") in ("lexical", "hybrid"):
+        """search_type "lexical" / "hybrid" / "grouped": a retriever over `lexical_search` /
+        `hybrid_search` / `similarity_search_grouped` with search_kwargs passed on; every other
+        type is the base class's."""
+        if kwargs.get("search_type") in ("lexical", "hybrid", "grouped"):
             return _LexicalRetriever(self, kwargs["search_type"], kwargs.get("search_kwargs"))
         return super().as_retriever(**kwargs)
 
