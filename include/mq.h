@@ -59,6 +59,7 @@ extern "C" {
 #define MQ_POOL_MEAN 1
 
 #define MQ_MAX_K 64    /* largest k one search call returns          */
+#define MQ_RANGE_MAX_HITS 4096 /* longest list of mq_index_search_range */
 
 typedef struct mq_index mq_index;
 typedef struct mq_encoder mq_encoder;
@@ -427,6 +428,64 @@ int mq_index_search_grouped(mq_index* ix, const float* queries, int64_t nq, int 
 int mq_debug_group_check(int dim, int64_t n_rows, const float* queries, int64_t nq, int k, const int32_t* codes,
                          int32_t n_groups, const float* out_scores, const int64_t* out_ids, const void* scratch,
                          int64_t scratch_bytes);
+
+/* Range search (K17; LangChain's "similarity_score_threshold" retriever, candidate lists
+ * longer than MQ_MAX_K for a reranker, and "how many rows are this similar"): every row at or
+ * above a score threshold, counted exactly, and the best max_hits of them.
+ * Inputs: the index rows; an optional device row mask `bits` in the layout of the masked
+ * search (NULL: every row); nq queries; min_score, a float (-inf: no threshold; NaN is
+ * refused); max_hits in [1, MQ_RANGE_MAX_HITS].
+ * Candidates: row r is a candidate of a query when the mask admits it.
+ * Scores: score(q, r) = the exact fp32 dot of the query, taken as given, with the stored row,
+ * as in the grouped search, + 0.0f (a -0.0 sum ranks as +0.0).  A hit is a candidate with
+ * score >= min_score, compared in fp32.  Hits rank by (score desc, row asc).
+ * Output: out_counts [nq] (int64) = the number of hits, exact, which may exceed max_hits;
+ * out_scores / out_ids [nq, max_hits] = the first min(count, max_hits) hits of the ranking,
+ * padded with (-inf, -1).  An empty index or an all-zero mask gives count 0 and padding only.
+ * Repeated calls return the same bits.
+ *
+ * range_score_kernel walks the rows as group_scan_kernel does (16 lanes per row, at most 16
+ * queries per pass, mq_range_scan_blocks(n, CUs) workgroups of 16 lane groups, two rows in
+ * flight per lane group) and writes keys[query][row], a uint32 [<= 16][n] array in the
+ * scratch: the score as an order-preserving unsigned for a hit (never 0 for a finite score),
+ * 0 for any other row; every cell of a pass is written exactly once.  The selection works on
+ * the unique 64-bit keys K = (keys[q][row] << 32) | (0xFFFFFFFF - row): a radix select over six
+ * digits of at most 11 bits from the top (range_hist_kernel: per-workgroup LDS histograms
+ * added into hist[query][bins]; range_pick_kernel: one workgroup per query fixes the digit in
+ * which the key of rank max_hits falls; the first histogram's total is the count) finds the
+ * cut K*, range_collect_kernel gathers the cells with K >= K* (one returning atomic add per
+ * wave) and range_sort_kernel sorts them in LDS and writes the list.  A query is settled, and
+ * its later histogram and pick launches return at once, when count <= max_hits or when the
+ * bin chosen at some digit is wanted whole.  The histogram and collect kernels run
+ * mq_range_select_blocks(n, CUs) workgroups per query, each over cells b * 256 + t,
+ * + 256 * blocks, ...  The launches are enqueued unconditionally: the call runs a fixed number
+ * of passes, reads nothing back in between, and has no overflow case to retry.  More than 16
+ * queries run as successive passes that reuse the scratch in stream order.
+ *
+ * queries [nq, dim] and the three outputs are all host (io_on_device = 0: staged through the
+ * scratch, the call synchronises) or all device (asynchronous on `stream`); bits and scratch
+ * are device memory of the index's GPU.  Checked before any HIP call, each with a message
+ * naming the offending value: max_hits, a NaN min_score, nq (these three before the handle is
+ * looked at), dim % 64 == 0 and dim <= 1024, n < 2^31, non-NULL buffers, scratch 16-byte
+ * aligned, at least mq_range_scratch_bytes(n, nq, max_hits) bytes and overlapping none of the
+ * outputs.  The call allocates and frees no device memory.  It reads the slab as it stood when
+ * the call began: an mq_index_add / _select / _reset / _load on the same handle must not run
+ * concurrently with it.
+ * mq_range_scratch_bytes is non-decreasing in every argument and bounded in nq (a multiple of
+ * 256; arguments out of range are clamped): 4 bytes x min(nq, 16) x n for the keys, plus, per
+ * query of a pass, an 8 KB histogram, 12 bytes per list entry (the candidates, which also
+ * stage a host call's ids, and its staged scores) and 4 KB of query staging - under 1 MB in
+ * all, about 65 MB at a million rows.  mq_debug_range_check runs the HIP-free checks alone on
+ * a stated index shape (dim, n_rows), for hosts without a GPU to make an index on. */
+int64_t mq_range_scratch_bytes(int64_t n_rows, int64_t nq, int max_hits);
+int mq_range_scan_blocks(int64_t n_rows, int compute_units);
+int mq_range_select_blocks(int64_t n_rows, int compute_units);
+int mq_index_search_range(mq_index* ix, const float* queries, int64_t nq, int max_hits, float min_score,
+                          const uint32_t* bits, int64_t* out_counts, float* out_scores, int64_t* out_ids,
+                          int io_on_device, void* scratch, int64_t scratch_bytes, void* stream);
+int mq_debug_range_check(int dim, int64_t n_rows, const float* queries, int64_t nq, int max_hits, float min_score,
+                         const int64_t* out_counts, const float* out_scores, const int64_t* out_ids,
+                         const void* scratch, int64_t scratch_bytes);
 
 /* Persistence: a flat binary slab (header + rows); written files are
  * fsync'ed before the call returns. */

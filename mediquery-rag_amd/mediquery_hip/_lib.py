@@ -21,6 +21,7 @@ MQ_DTYPE_F32, MQ_DTYPE_BF16, MQ_DTYPE_F32X6, MQ_DTYPE_F32_SCREEN = 0, 1, 2, 3
 MQ_GELU_ERF, MQ_GELU_TANH = 0, 1
 MQ_POOL_CLS, MQ_POOL_MEAN = 0, 1
 MQ_MAX_K = 64
+MQ_RANGE_MAX_HITS = 4096         # longest list of mq_index_search_range (its count is not bounded)
 MQ_HEAD_MAX_LABELS = 8           # most labels a cross-encoder head carries (mq_encoder_load_head)
 MQ_MASK_SET, MQ_MASK_AND, MQ_MASK_OR, MQ_MASK_CLEAR = 0, 1, 2, 3
 MQ_CONTAINS_MAX_BYTES = 256      # longest mq_mask_contains pattern (UTF-8 bytes)
@@ -118,6 +119,11 @@ SIGNATURES = {
     "mq_group_scan_blocks": (_I, [_I64, _I]),
     "mq_index_search_grouped": (_I, [_P, _P, _I64, _I, _P, ctypes.c_int32, _P, _P, _P, _I, _P, _I64, _P]),
     "mq_debug_group_check": (_I, [_I, _I64, _P, _I64, _I, _P, ctypes.c_int32, _P, _P, _P, _I64]),
+    "mq_range_scratch_bytes": (_I64, [_I64, _I64, _I]),
+    "mq_range_scan_blocks": (_I, [_I64, _I]),
+    "mq_range_select_blocks": (_I, [_I64, _I]),
+    "mq_index_search_range": (_I, [_P, _P, _I64, _I, ctypes.c_float, _P, _P, _P, _P, _I, _P, _I64, _P]),
+    "mq_debug_range_check": (_I, [_I, _I64, _P, _I64, _I, ctypes.c_float, _P, _P, _P, _P, _I64]),
     "mq_topk_merge_host": (_I, [_P, _P, _I, _I64, _I, _I, _P, _P]),
     "mq_topk_merge_device": (_I, [_P, _P, _I, _I64, _I, _I, _P, _P, _P]),
     "mq_encoder_create": (_I, [_I, ctypes.POINTER(BertConfigC), _PP]),

@@ -67,11 +67,21 @@ except Exception:
             mmr_kwargs = {a: search_kwargs[a] for a in ("k", "fetch_k", "lambda_mult", "filter", "where_document")
                           if a in search_kwargs}
             sim_kwargs = {a: search_kwargs[a] for a in ("filter", "where_document") if a in search_kwargs}
+            # search_type="similarity_score_threshold": score_threshold, k, filter and
+            # where_document go to similarity_search_with_relevance_scores; a missing or
+            # non-float threshold is refused here, as LangChain's retriever refuses it
+            thresh = kwargs.get("search_type") == "similarity_score_threshold"
+            thresh_kwargs = {a: search_kwargs[a] for a in ("score_threshold", "k", "filter", "where_document")
+                             if a in search_kwargs}
+            if thresh and not isinstance(search_kwargs.get("score_threshold"), float):
+                raise ValueError("`score_threshold` is not specified with a float value(0~1) in `search_kwargs`.")
 
             class _Retriever:
                 def invoke(self, query, **_):
                     if mmr:
                         return store.max_marginal_relevance_search(query, **mmr_kwargs)
+                    if thresh:
+                        return [d for d, _ in store.similarity_search_with_relevance_scores(query, **thresh_kwargs)]
                     return store.similarity_search(query, k=k, **sim_kwargs)
 
                 get_relevant_documents = invoke

@@ -282,6 +282,68 @@ class FlatIndex:
                       _lib.ptr(bits), _lib.ptr(out_scores), _lib.ptr(out_ids), 1, _lib.ptr(scratch),
                       scratch.numel() * scratch.element_size(), _lib.stream_handle(stream))
 
+    def _range_args(self, bits, scratch, nq, max_hits, min_score):
+        """The device checks of the range calls -> (max_hits, min_score, scratch)."""
+        import torch
+        n, max_hits, min_score = len(self), int(max_hits), float(min_score)
+        if not 1 <= max_hits <= _lib.MQ_RANGE_MAX_HITS:
+            raise ValueError("max_hits must be in [1, %d] (got %d)" % (_lib.MQ_RANGE_MAX_HITS, max_hits))
+        if min_score != min_score:
+            raise ValueError("min_score must not be NaN (-inf means no threshold)")
+        if self.dim % 64 or self.dim > 1024:
+            raise ValueError("the range scan serves dim %% 64 == 0, dim <= 1024 (got %d)" % self.dim)
+        if bits is not None:
+            self._check_bits(bits)
+        need = range_scratch_bytes(n, nq, max_hits)
+        if scratch is None:
+            scratch = torch.empty(max(need, 256), dtype=torch.uint8, device=torch.device("cuda", int(self.device)))
+        if not (getattr(scratch, "is_cuda", False) and scratch.is_contiguous()
+                and scratch.device.index == int(self.device)
+                and scratch.numel() * scratch.element_size() >= need and scratch.data_ptr() % 16 == 0):
+            raise ValueError("scratch must be a contiguous 16-byte aligned tensor of >= %d bytes on cuda:%d"
+                             % (need, self.device))
+        return max_hits, min_score, scratch
+
+    def search_range(self, queries, max_hits, min_score=-np.inf, bits=None, scratch=None):
+        """Range search (K17, mq_index_search_range): the rows whose exact fp32 score is >=
+        min_score (-inf: every row), among those `bits` admits (a row mask as for
+        search_masked; None = every row).  scratch: range_scratch_bytes(n, nq, max_hits) device
+        bytes (None: a torch.empty of that size).  -> (counts [nq] int64, scores [nq, max_hits],
+        ids [nq, max_hits]): the exact number of hits, which may exceed max_hits, and the first
+        min(count, max_hits) of them by (score desc, row asc), padded with (-inf, -1)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        with _lib.device_scope(self.device):
+            max_hits, min_score, scratch = self._range_args(bits, scratch, q.shape[0], max_hits, min_score)
+            counts = np.empty(q.shape[0], dtype=np.int64)
+            scores = np.empty((q.shape[0], max_hits), dtype=np.float32)
+            ids = np.empty((q.shape[0], max_hits), dtype=np.int64)
+            _lib.call("mq_index_search_range", self._h, _lib.ptr(q), q.shape[0], max_hits, min_score, _lib.ptr(bits),
+                      _lib.ptr(counts), _lib.ptr(scores), _lib.ptr(ids), 0, _lib.ptr(scratch),
+                      scratch.numel() * scratch.element_size(), _lib.stream_handle(None))
+        return counts, scores, ids
+
+    def search_range_device(self, queries, max_hits, out_counts, out_scores, out_ids, min_score=-np.inf, bits=None,
+                            scratch=None, stream=None):
+        """search_range on torch device tensors (queries [nq, dim] f32, out_counts [nq] int64,
+        out_scores [nq, max_hits] f32, out_ids [nq, max_hits] int64), asynchronous on the given
+        (or current) torch stream."""
+        import torch
+        nq = queries.shape[0]
+        for t, dt, cnt in ((queries, torch.float32, nq * self.dim), (out_counts, torch.int64, nq),
+                           (out_scores, torch.float32, nq * int(max_hits)), (out_ids, torch.int64, nq * int(max_hits))):
+            if not (getattr(t, "is_cuda", False) and t.dtype == dt and t.is_contiguous()
+                    and t.device.index == int(self.device) and t.numel() >= cnt):
+                raise ValueError("queries / out_counts / out_scores / out_ids must be contiguous float32 / int64 / "
+                                 "float32 / int64 tensors of [nq, dim] / [nq] / [nq, max_hits] / [nq, max_hits] on "
+                                 "cuda:%d" % self.device)
+        with _lib.device_scope(self.device):
+            max_hits, min_score, scratch = self._range_args(bits, scratch, nq, max_hits, min_score)
+            if scratch.data_ptr() in (out_counts.data_ptr(), out_scores.data_ptr(), out_ids.data_ptr()):
+                raise ValueError("scratch must not be one of the outputs")
+            _lib.call("mq_index_search_range", self._h, _lib.ptr(queries), nq, max_hits, min_score, _lib.ptr(bits),
+                      _lib.ptr(out_counts), _lib.ptr(out_scores), _lib.ptr(out_ids), 1, _lib.ptr(scratch),
+                      scratch.numel() * scratch.element_size(), _lib.stream_handle(stream))
+
     @property
     def masked_gathers(self):
         """Masked searches the int8 screen did not certify (answered from gathered rows)."""
@@ -308,6 +370,24 @@ def group_scan_blocks(n_rows, compute_units):
     """Workgroups of the grouped scan over n_rows on a GPU of compute_units CUs; each holds 16
     lane groups, and lane group g walks rows g, g + 16 * blocks, ..., two per iteration."""
     return int(_lib.lib().mq_group_scan_blocks(int(n_rows), int(compute_units)))
+
+
+def range_scratch_bytes(n_rows, nq, max_hits=_lib.MQ_RANGE_MAX_HITS):
+    """Bytes of device scratch mq_index_search_range wants for n_rows rows, nq queries and lists
+    of max_hits; non-decreasing in every argument and bounded in nq."""
+    return int(_lib.lib().mq_range_scratch_bytes(int(n_rows), int(nq), int(max_hits)))
+
+
+def range_scan_blocks(n_rows, compute_units):
+    """Workgroups of the range scan over n_rows on a GPU of compute_units CUs: the grouped
+    scan's geometry (16 lane groups each, lane group g walks rows g, g + 16 * blocks, ...)."""
+    return int(_lib.lib().mq_range_scan_blocks(int(n_rows), int(compute_units)))
+
+
+def range_select_blocks(n_rows, compute_units):
+    """Workgroups per query of the range search's histogram and collect kernels; workgroup b
+    walks cells b * 256 + t, + 256 * blocks, ..."""
+    return int(_lib.lib().mq_range_select_blocks(int(n_rows), int(compute_units)))
 
 
 def merge_topk_host(scores, ids, k_out):

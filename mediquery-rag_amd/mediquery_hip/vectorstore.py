@@ -39,6 +39,15 @@ and by the device group scan otherwise (mq_index_search_grouped, the definition:
 "Grouped search"); `as_retriever(search_type="grouped")` wraps it, and
 `parent_retriever.HipParentDocumentRetriever` maps the children back to their parents.
 
+Range retrieval (LangChain's "similarity_score_threshold" retriever, candidate lists for a
+reranker, counting): `similarity_search_range*` returns every row whose cosine to the query is at
+least `min_cosine`, nearest first, up to `limit` <= MQ_RANGE_MAX_HITS (4096) of them, as a
+`RangeResult` whose `total` is the exact number of such rows; `count_similar` returns that number
+alone.  One device call (mq_index_search_range, the definition: include/mq.h "Range search"),
+always in exact fp32.  `similarity_search_with_relevance_scores(score_threshold=...)` filters the
+ordinary top-k the way LangChain's base class does, and `as_retriever` takes
+`search_type="similarity_score_threshold"` and `"range"`.
+
 Persistence: `mq_<collection>.json` (ids, documents, metadatas, and the name of the slab
 file) is the base commit point; a full write (the first write, `delete`, an upsert that
 replaces rows, an explicit `persist()`) puts the rows in a fresh `mq_<collection>.<gen>.flat`
@@ -66,7 +75,7 @@ from . import _lib
 from .compat import Document, VectorStoreBase
 from .native import (FlatIndex, group_scratch_bytes, lex_batch_scratch_bytes, lex_df, lex_df_batch,
                      lex_scratch_bytes, lex_topk, lex_topk_batch, mask_combine, mask_contains, mask_eval,
-                     mask_eval_bits)
+                     mask_eval_bits, range_scratch_bytes)
 
 # `*_batch` lexical / hybrid calls of at least this many queries take the batched scan
 # (mq_lex_topk_batch); fewer take the single-query path.  Measured at 1M rows (DESIGN.md, K15,
@@ -614,8 +623,45 @@ def collapse_candidates(ids, scores, codes, k):
     return rows, out, len(seen) >= k or valid < _lib.MQ_MAX_K
 
 
+class RangeResult(list):
+    """What the range searches return: a list (nearest first, at most `limit` entries) with one
+    attribute, `total`: the number of rows at or above the threshold, >= len."""
+
+    def __init__(self, items=(), total=None):
+        super().__init__(items)
+        self.total = len(self) if total is None else int(total)
+        if self.total < len(self):
+            raise ValueError("total %d is below the %d entries of the list" % (self.total, len(self)))
+
+
+def _check_limit(limit, n_candidates):
+    """Length of a range search's list over n_candidates rows; raises past the device limit."""
+    kk = min(int(limit), int(n_candidates))
+    if kk > _lib.MQ_RANGE_MAX_HITS:
+        raise ValueError("a range search returning up to %d results (limit=%d over %d rows) exceeds the device "
+                         "list limit MQ_RANGE_MAX_HITS=%d" % (kk, limit, n_candidates, _lib.MQ_RANGE_MAX_HITS))
+    return kk
+
+
+def _check_min_cosine(min_cosine):
+    """None (no threshold) -> -inf; a finite number -> float; anything else raises."""
+    if min_cosine is None:
+        return -math.inf
+    if isinstance(min_cosine, bool) or not isinstance(min_cosine, (int, float, np.integer, np.floating)) \
+            or not math.isfinite(min_cosine):
+        raise ValueError("min_cosine must be None or a finite number, got %r" % (min_cosine,))
+    return float(min_cosine)
+
+
+def _check_score_threshold(score_threshold):
+    if isinstance(score_threshold, bool) or not isinstance(score_threshold, (int, float, np.integer, np.floating)) \
+            or math.isnan(score_threshold):
+        raise ValueError("score_threshold must be a number, got %r" % (score_threshold,))
+    return float(score_threshold)
+
+
 class _LexicalRetriever:
-    """What `HipChroma.as_retriever(search_type="lexical" | "hybrid" | "grouped")` returns:
+    """What `HipChroma.as_retriever(search_type="lexical" | "hybrid" | "grouped" | "range")` returns:
     `invoke` / `get_relevant_documents` call the store's method with the retriever's
     search_kwargs."""
 
@@ -626,7 +672,8 @@ class _LexicalRetriever:
 
     def invoke(self, query, config=None, **kwargs):
         fn = {"lexical": self.vectorstore.lexical_search, "hybrid": self.vectorstore.hybrid_search,
-              "grouped": self.vectorstore.similarity_search_grouped}[self.search_type]
+              "grouped": self.vectorstore.similarity_search_grouped,
+              "range": self.vectorstore.similarity_search_range}[self.search_type]
         return fn(query, **self.search_kwargs)
 
     get_relevant_documents = invoke
@@ -748,6 +795,7 @@ class HipChroma(VectorStoreBase):
         self.group_scans = 0           # grouped queries the top-64 did not certify (sent to the scan)
         self._group_scratch = None     # the group scan's device scratch, grown on demand
         self._group_absent = None      # ((key, codes version), some row lacks the key)
+        self._range_scratch = None     # the range search's device scratch, grown on demand
         if search_precision not in SEARCH_PRECISIONS:
             raise ValueError("search_precision must be one of %s, got %r"
                              % (sorted(SEARCH_PRECISIONS), search_precision))
@@ -1330,6 +1378,100 @@ class HipChroma(VectorStoreBase):
         return [[self._doc(r) for r, _ in rows]
                 for rows in self._grouped_rows(q, k, group_by, filter, where_document, _force_scan)]
 
+    # ---- range search: every row at or above a cosine threshold ----------------------------
+    def _range_room(self, n, nq, limit):
+        """The range search's scratch: grows on demand and is kept."""
+        import torch
+        need = range_scratch_bytes(n, nq, limit)
+        if self._range_scratch is None or self._range_scratch.numel() < need:
+            self._range_scratch = None  # release before growing
+            with _lib.device_scope(self._device):
+                self._range_scratch = torch.empty(need, dtype=torch.uint8, device=torch.device("cuda", self._device))
+        return self._range_scratch
+
+    def _range_rows(self, q, min_cosine=None, limit=None, filter=None, where_document=None):
+        """-> per query ([(row, cosine)], total): the rows whose cosine to the query is >=
+        min_cosine (None: every row; rounded to fp32, the arithmetic of the comparison), among
+        those `filter` / `where_document` admit, best first, at most `limit` of them (None:
+        MQ_RANGE_MAX_HITS), and their exact number (include/mq.h, "Range search").  `limit` is
+        clipped to the candidate rows and must then fit MQ_RANGE_MAX_HITS.  One
+        mq_index_search_range call for the batch, in exact fp32 whatever search_precision is."""
+        if where_document is not None:
+            _check_where_document(where_document)
+        min_score = _check_min_cosine(min_cosine)
+        limit = _lib.MQ_RANGE_MAX_HITS if limit is None else int(limit)
+        q = np.ascontiguousarray(q, dtype=np.float32).reshape(-1, self._dim or 1)
+        n = 0 if self._index is None else len(self._index)
+        if n == 0 or not len(q):
+            return [([], 0) for _ in range(len(q))]
+        if self._dim % 64 or self._dim > 1024:
+            raise ValueError("range search serves stores of dim %% 64 == 0, dim <= 1024 (this store's dim is %d)"
+                             % self._dim)
+        bits = None
+        if filter or where_document is not None:
+            _, bits = self._admit(1, filter, where_document)
+        if limit > _lib.MQ_RANGE_MAX_HITS:  # the candidate count decides between raising and clipping
+            limit = _check_limit(limit, n if bits is None else int(self._mask_rows(bits).sum()))
+        hits = max(1, min(limit, n))        # limit <= 0: the count alone
+        counts, s, i = self._index.search_range(q, hits, min_score, bits, self._range_room(n, len(q), hits))
+        keep = max(0, min(limit, hits))
+        return [([(int(r), float(c)) for r, c in zip(ij[:keep], sj[:keep]) if r >= 0], int(cj))
+                for cj, sj, ij in zip(counts, s, i)]
+
+    def similarity_search_range_by_vector_with_score(self, embedding, min_cosine=None, limit=None, filter=None,
+                                                     where_document=None, **kwargs):
+        """(Document, squared L2 distance) of every row whose cosine to `embedding` is >=
+        min_cosine, nearest first (ties: insertion order): a `RangeResult` of at most `limit`
+        (None: MQ_RANGE_MAX_HITS) entries whose `total` counts them all."""
+        rows, total = self._range_rows(embedding, min_cosine, limit, filter, where_document)[0]
+        return RangeResult([(self._doc(r), max(0.0, 2.0 - 2.0 * c)) for r, c in rows], total)
+
+    def similarity_search_range_with_score(self, query, min_cosine=None, limit=None, filter=None,
+                                           where_document=None, **kwargs):
+        if where_document is not None:
+            _check_where_document(where_document)
+        _check_min_cosine(min_cosine)
+        if self._index is None or len(self._index) == 0:
+            return RangeResult()
+        return self.similarity_search_range_by_vector_with_score(self._embed_query(query), min_cosine, limit, filter,
+                                                                 where_document)
+
+    def similarity_search_range(self, query, min_cosine=None, limit=None, filter=None, where_document=None,
+                                **kwargs):
+        hits = self.similarity_search_range_with_score(query, min_cosine, limit, filter, where_document)
+        return RangeResult([d for d, _ in hits], hits.total)
+
+    def similarity_search_range_batch(self, queries, min_cosine=None, limit=None, filter=None,
+                                      where_document=None):
+        """Many queries: one encoder batch and one device call -> a `RangeResult` of Documents
+        per query."""
+        if where_document is not None:
+            _check_where_document(where_document)
+        _check_min_cosine(min_cosine)
+        queries = list(queries)
+        n = 0 if self._index is None else len(self._index)
+        if n == 0 or not queries:
+            return [RangeResult() for _ in queries]
+        if hasattr(self._embedding_function, "embed_array"):
+            q = self._embedding_function.embed_array(queries)
+        else:
+            q = np.asarray(self._embedding_function.embed_documents(queries), np.float32)
+        return [RangeResult([self._doc(r) for r, _ in rows], total)
+                for rows, total in self._range_rows(q, min_cosine, limit, filter, where_document)]
+
+    def count_similar_by_vector(self, embedding, min_cosine, filter=None, where_document=None):
+        """The number of rows whose cosine to `embedding` is >= min_cosine, among those `filter`
+        / `where_document` admit: the count of the range search, no list."""
+        return self._range_rows(embedding, min_cosine, 1, filter, where_document)[0][1]
+
+    def count_similar(self, query, min_cosine, filter=None, where_document=None):
+        if where_document is not None:
+            _check_where_document(where_document)
+        _check_min_cosine(min_cosine)
+        if self._index is None or len(self._index) == 0:
+            return 0
+        return self.count_similar_by_vector(self._embed_query(query), min_cosine, filter, where_document)
+
     # ---- lexical (BM25) and hybrid (reciprocal rank fusion) retrieval ----------------------
     def _lex_tok(self):
         tok = self._lex_tokenizer
@@ -1469,10 +1611,13 @@ class HipChroma(VectorStoreBase):
                 for hits in self._hybrid(queries, k, fetch_k, weights, c, filter, where_document)]
 
     def as_retriever(self, **kwargs):
-        """search_type "lexical" / "hybrid" / "grouped": a retriever over `lexical_search` /
-        `hybrid_search` / `similarity_search_grouped` with search_kwargs passed on; every other
-        type is the base class's."""
-        if kwargs.get("search_type") in ("lexical", "hybrid", "grouped"):
+        """search_type "lexical" / "hybrid" / "grouped" / "range": a retriever over
+        `lexical_search` / `hybrid_search` / `similarity_search_grouped` /
+        `similarity_search_range` with search_kwargs passed on (range: min_cosine, limit, filter,
+        where_document); every other type is the base class's, "similarity_score_threshold"
+        (score_threshold, k, filter, where_document -> `similarity_search_with_relevance_scores`)
+        among them."""
+        if kwargs.get("search_type") in ("lexical", "hybrid", "grouped", "range"):
             return _LexicalRetriever(self, kwargs["search_type"], kwargs.get("search_kwargs"))
         return super().as_retriever(**kwargs)
 
@@ -1481,9 +1626,16 @@ class HipChroma(VectorStoreBase):
             return self.override_relevance_score_fn
         return lambda d: 1.0 - d / math.sqrt(2)  # LangChain's euclidean relevance
 
-    def similarity_search_with_relevance_scores(self, query, k=DEFAULT_K, **kwargs):
+    def similarity_search_with_relevance_scores(self, query, k=DEFAULT_K, score_threshold=None, **kwargs):
+        """(Document, relevance) of the top k; with `score_threshold`, the pairs of them whose
+        relevance is >= it (the filter of LangChain's base class, whatever relevance_score_fn is)."""
+        if score_threshold is not None:
+            score_threshold = _check_score_threshold(score_threshold)
         fn = self._select_relevance_score_fn()
-        return [(d, fn(s)) for d, s in self.similarity_search_with_score(query, k, **kwargs)]
+        pairs = [(d, fn(s)) for d, s in self.similarity_search_with_score(query, k, **kwargs)]
+        if score_threshold is not None:
+            pairs = [(d, r) for d, r in pairs if r >= score_threshold]
+        return pairs
 
     # ---- constructors ------------------------------------------------------------------
     @classmethod
