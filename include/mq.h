@@ -502,7 +502,11 @@ int mq_index_load_append(mq_index* ix, const char* path);
 /* Host-side k-way merge of per-shard candidate lists (the step after the RCCL
  * all-gather).  scores/ids are [n_lists, nq, k_in] (list-major, as an
  * all-gather stacks them); output [nq, k_out] by (score desc, id asc); ids < 0 are
- * padding.  Pure CPU, no device needed. */
+ * padding.  Pure CPU, no device needed.
+ * Preconditions of both merges (the callers' to keep, not checked): the valid ids of a
+ * query are distinct across its lists (the device merge places an entry by counting the
+ * entries better than it); no score is NaN.  -0.0 ranks as +0.0: the two tie and the
+ * lower id (compared as unsigned) goes first; -inf with a valid id ranks above padding. */
 int mq_topk_merge_host(const float* scores, const int64_t* ids, int n_lists, int64_t nq,
                        int k_in, int k_out, float* out_scores, int64_t* out_ids);
 /* Same merge on the device (inputs/outputs device pointers, async on stream).  Each
@@ -830,6 +834,22 @@ int mq_debug_cls_head(const float* cls, int B, int H, const float* pooler_w, con
  * stats[0] = max ||c - scale r8||, stats[1] = max ||scale r8||.  For kernel unit tests. */
 int mq_debug_int8_screen(mq_index* ix, const float* query, int kc, float* out_scores, int64_t* out_ids,
                          float* stats);
+
+/* The device merge (K10) with every choice the library makes for it in the caller's hands,
+ * on device buffers, asynchronous on `stream`; it launches the product's kernels unchanged.
+ * scores / ids are [n_lists, nq, k_in] as for mq_topk_merge_device, ids int32 (id_bits 32,
+ * what the index's own scans hand over) or int64 (id_bits 64); out_scores / out_ids
+ * [nq, k_out].  list_kc: 0 = no truncated-list check, else 1 <= list_kc <= k_in, the
+ * entries a scan kept per list (overflow bit 0 is tested at position list_kc - 1).  kc: 0 =
+ * the library's thread-list length for k_out, else 8, 16 or 64 (kc < k_out is exact only
+ * where bit 1 stays clear).  form: 0 = the library's pick (thread lists iff k_out <= 16
+ * and nq > 32), 1 = the thread-list kernel, 2 = the threshold kernel (which falls back to
+ * thread lists past 4096 lists or 2048 survivors).  flag: NULL = no overflow checks, else
+ * one int the call zeroes on the stream first; bit 0 = a truncated list may hide a member
+ * of the top k_out, bit 1 = a thread list may have dropped one.  For kernel unit tests. */
+int mq_debug_topk_merge(const float* scores, const void* ids, int id_bits, int n_lists, int64_t nq,
+                        int k_in, int k_out, int list_kc, int kc, int form,
+                        float* out_scores, int64_t* out_ids, int* flag, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1110,8 +1110,9 @@ __global__ __launch_bounds__(256) void merge_kernel(const float* __restrict__ cs
 constexpr int kSelCap = 2048;
 constexpr int kSelHeads = 16;  // heads per thread: n_lists <= 4096
 
-__device__ __forceinline__ unsigned score_key(float x) {  // order-preserving, > 0
-  const unsigned b = __float_as_uint(x);
+// order-preserving, > 0; -0.0 keys as +0.0, which better() ties it with
+__device__ __forceinline__ unsigned score_key(float x) {
+  const unsigned b = x == 0.0f ? 0u : __float_as_uint(x);
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
@@ -1423,11 +1424,12 @@ void launch_search(const mq_index* ix, const float* q, int nq, int k, int G, int
 
 template <int KC, typename IdIn>
 void launch_merge(const float* cs, const IdIn* ci, int n_lists, int64_t nq, int k_in, int k_out,
-                  float* os, int64_t* oi, int list_kc, int* overflow, hipStream_t s) {
+                  float* os, int64_t* oi, int list_kc, int* overflow, hipStream_t s, int form = 0) {
   // k_out <= 16 over a batch: register thread lists (25 us at B = 256); larger k_out or
   // a few queries: the threshold merge (k_out = 64: 38 us vs 96 us with 16-entry thread
-  // lists + overflow check; one query's 512 stream lists, k_out = 16: 29 vs 48 us)
-  if (k_out <= 16 && nq > 32)
+  // lists + overflow check; one query's 512 stream lists, k_out = 16: 29 vs 48 us).
+  // form 1 / 2 force the thread-list / threshold kernel (mq_debug_topk_merge only)
+  if (form ? form == 1 : (k_out <= 16 && nq > 32))
     hipLaunchKernelGGL((merge_kernel<KC, IdIn>), dim3((unsigned)nq), dim3(256), 0, s, cs, ci,
                        n_lists, nq, k_in, k_out, os, oi, list_kc, overflow);
   else
@@ -1438,11 +1440,11 @@ void launch_merge(const float* cs, const IdIn* ci, int n_lists, int64_t nq, int 
 template <typename IdIn>
 void merge_dispatch(const float* cs, const IdIn* ci, int n_lists, int64_t nq, int k_in, int k_out,
                     float* os, int64_t* oi, hipStream_t s, int list_kc = 1 << 30,
-                    int* overflow = nullptr, int kc = 0) {
+                    int* overflow = nullptr, int kc = 0, int form = 0) {
   switch (kc ? kc : kc_merge(k_out)) {
-    case 8: launch_merge<8>(cs, ci, n_lists, nq, k_in, k_out, os, oi, list_kc, overflow, s); break;
-    case 16: launch_merge<16>(cs, ci, n_lists, nq, k_in, k_out, os, oi, list_kc, overflow, s); break;
-    default: launch_merge<64>(cs, ci, n_lists, nq, k_in, k_out, os, oi, list_kc, overflow, s); break;
+    case 8: launch_merge<8>(cs, ci, n_lists, nq, k_in, k_out, os, oi, list_kc, overflow, s, form); break;
+    case 16: launch_merge<16>(cs, ci, n_lists, nq, k_in, k_out, os, oi, list_kc, overflow, s, form); break;
+    default: launch_merge<64>(cs, ci, n_lists, nq, k_in, k_out, os, oi, list_kc, overflow, s, form); break;
   }
 }
 
@@ -2901,6 +2903,34 @@ int mq_topk_merge_device(const float* scores, const int64_t* ids, int n_lists, i
   MQ_CHECK_ARG(scores && ids && out_scores && out_ids, "NULL buffer");
   merge_dispatch<int64_t>(scores, ids, n_lists, nq, k_in, k_out, out_scores, out_ids,
                           (hipStream_t)stream);
+  MQ_HIP(hipGetLastError());
+  return MQ_OK;
+}
+
+int mq_debug_topk_merge(const float* scores, const void* ids, int id_bits, int n_lists, int64_t nq,
+                        int k_in, int k_out, int list_kc, int kc, int form, float* out_scores,
+                        int64_t* out_ids, int* flag, void* stream) {
+  clear_error();
+  MQ_CHECK_ARG(id_bits == 32 || id_bits == 64, "id_bits must be 32 or 64 (got %d)", id_bits);
+  MQ_CHECK_ARG(n_lists >= 1, "n_lists must be >= 1 (got %d)", n_lists);
+  MQ_CHECK_ARG(nq >= 0 && nq <= 0x7fffffff, "nq must be in [0, 2^31) (got %lld)", (long long)nq);
+  MQ_CHECK_ARG(k_in >= 1, "k_in must be >= 1 (got %d)", k_in);
+  MQ_CHECK_ARG(k_out >= 1 && k_out <= MQ_MAX_K, "k_out must be in [1, %d] (got %d)", MQ_MAX_K, k_out);
+  MQ_CHECK_ARG(list_kc >= 0 && list_kc <= k_in, "list_kc must be 0 or in [1, k_in = %d] (got %d)", k_in,
+               list_kc);
+  MQ_CHECK_ARG(kc == 0 || kc == 8 || kc == 16 || kc == 64, "kc must be 0, 8, 16 or 64 (got %d)", kc);
+  MQ_CHECK_ARG(form >= 0 && form <= 2, "form must be 0, 1 or 2 (got %d)", form);
+  if (nq == 0) return MQ_OK;
+  MQ_CHECK_ARG(scores && ids && out_scores && out_ids, "NULL buffer");
+  hipStream_t s = (hipStream_t)stream;
+  if (flag) MQ_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
+  const int lkc = list_kc ? list_kc : 1 << 30;
+  if (id_bits == 32)
+    merge_dispatch<int>(scores, (const int*)ids, n_lists, nq, k_in, k_out, out_scores, out_ids, s, lkc, flag,
+                        kc, form);
+  else
+    merge_dispatch<int64_t>(scores, (const int64_t*)ids, n_lists, nq, k_in, k_out, out_scores, out_ids, s,
+                            lkc, flag, kc, form);
   MQ_HIP(hipGetLastError());
   return MQ_OK;
 }

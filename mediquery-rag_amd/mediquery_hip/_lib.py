@@ -163,6 +163,7 @@ SIGNATURES = {
                                 ctypes.c_float, _P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _I64, _P]),
     "mq_debug_ln_pool": (_I, [_P, _I, _I64, _P, _I, _I, _I, _I, _P, _P, ctypes.c_float, _I, _P, _I, _P]),
     "mq_debug_int8_screen":(_I, [_P, _P, _I, _P, _P, _P]),
+    "mq_debug_topk_merge": (_I, [_P, _P, _I, _I, _I64, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
 }
 
 _lib = None
