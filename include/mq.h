@@ -487,6 +487,65 @@ int mq_debug_range_check(int dim, int64_t n_rows, const float* queries, int64_t 
                          const int64_t* out_counts, const float* out_scores, const int64_t* out_ids,
                          const void* scratch, int64_t scratch_bytes);
 
+/* Self-join (K18; near-duplicate detection, LangChain's EmbeddingsRedundantFilter at index
+ * scale): which stored rows are near-copies of other stored rows.
+ * Inputs: the index rows; an optional device row mask `bits` in the layout of the masked search
+ * (NULL: every row); an optional list of left rows, left_rows int64 [n_left], distinct and each
+ * in [0, n) (NULL: rows 0 .. n - 1, and n_left must be n); min_score, a float (-inf is allowed;
+ * NaN is refused).
+ * Score: score(i, j) is exactly what mq_index_search_range returns for row j when the query is
+ * stored row i: range_score_kernel's fp32 FMA chain and 16-lane butterfly, + 0.0f.  The chain's
+ * order depends on the coordinate index alone, so score(i, j) and score(j, i) have the same bits.
+ * Partner: j is a partner of left row i when the mask admits both i and j, j != i and
+ * score(i, j) >= min_score in fp32.
+ * Outputs, all [n_left]: out_counts (int64) the number of partners; out_first the smallest
+ * partner row, or -1; out_nearest the partner that ranks first by (score desc, row asc), or -1;
+ * out_nearest_scores that partner's score, or -inf.  A left row outside the mask gets
+ * (0, -1, -1, -inf).  out_info is int64 [4]: [0] the sum of the counts, [1] left rows answered by
+ * the screen, [2] screen candidates that were verified, [3] left rows answered by the exact
+ * walk.  Repeated calls return the same bits.  An empty index or n_left = 0 succeeds and writes
+ * nothing but out_info.
+ *
+ * mode: MQ_JOIN_EXACT walks the fp32 slab once per 16 left rows (join_exact_kernel: the range
+ * search's row walk with the left rows staged in LDS by index; the lane that owns (row, left)
+ * keeps a running count, first and best key, each workgroup stores one partial per left row and
+ * join_finish_kernel folds them in a fixed order - no atomics).  MQ_JOIN_SCREEN (dim 256, 512 or
+ * 768; refused otherwise) takes the left rows in panels of 256: join_tau_kernel gathers the
+ * panel's rows from the bf16 shadow and sets tau = min_score - E, E a proven bound on
+ * |score - bf16 score| from the shadow's rounding maxima (csrc/join.hip); the bf16 threshold
+ * scan's appending pass lists every pair whose bf16 MFMA score clears tau; join_verify_kernel
+ * recomputes the listed pairs with the exact chain.  A left row with more than 4096 listed
+ * pairs goes to a redo list that the exact walk serves after the last panel, so the modes
+ * return identical outputs (out_info aside).  MQ_JOIN_AUTO screens where the dim allows it and
+ * the index holds at least 1024 rows, and walks otherwise.
+ *
+ * left_rows, the four outputs and out_info are all host (io_on_device = 0: staged through the
+ * scratch) or all device; bits and scratch are device memory of the index's GPU.  Unlike the
+ * range search the call always synchronises `stream` before it returns: the redo count is read
+ * back.  Checked before any HIP call, each with a message naming the offending value: a NaN
+ * min_score, mode, n_left (these before the handle is looked at), dim % 64 == 0 and dim <= 1024,
+ * MQ_JOIN_SCREEN's dims, n < 2^31, n_left == n under a NULL left_rows, non-NULL buffers, scratch
+ * 16-byte aligned, at least mq_join_scratch_bytes(n, n_left) bytes and overlapping none of the
+ * other buffers.  Host left rows outside [0, n) are refused; a device left row outside [0, n)
+ * is treated as a row outside the mask.  The call allocates no device memory of its own (the
+ * screen brings the index's bf16 shadow up to date, as a bf16 search does) and reads the slab as
+ * it stood when the call began.
+ * mq_join_scratch_bytes is non-decreasing in both arguments (a multiple of 256; arguments out of
+ * range are clamped): about 9 MB for a panel's survivor lists, plus 40 bytes per left row.
+ * mq_debug_join_check runs the HIP-free checks alone on a stated index shape (dim, n_rows). */
+#define MQ_JOIN_AUTO 0
+#define MQ_JOIN_EXACT 1
+#define MQ_JOIN_SCREEN 2
+int64_t mq_join_scratch_bytes(int64_t n_rows, int64_t n_left);
+int mq_index_self_join(mq_index* ix, float min_score, const uint32_t* bits, const int64_t* left_rows, int64_t n_left,
+                       int mode, int64_t* out_counts, int64_t* out_first, int64_t* out_nearest,
+                       float* out_nearest_scores, int64_t* out_info, int io_on_device, void* scratch,
+                       int64_t scratch_bytes, void* stream);
+int mq_debug_join_check(int dim, int64_t n_rows, float min_score, int mode, const int64_t* left_rows, int64_t n_left,
+                        const int64_t* out_counts, const int64_t* out_first, const int64_t* out_nearest,
+                        const float* out_nearest_scores, const int64_t* out_info, const void* scratch,
+                        int64_t scratch_bytes);
+
 /* Persistence: a flat binary slab (header + rows); written files are
  * fsync'ed before the call returns. */
 int mq_index_save(mq_index* ix, const char* path);

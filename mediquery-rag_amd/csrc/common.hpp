@@ -87,6 +87,16 @@ struct DeviceGuard {
   }
 };
 
+// Internal, not part of the ABI: the index's bf16 shadow for join.hip.  index_shadow (index.hip)
+// brings the shadow up to date with the stored rows on `s` (ensure_shadow, under the index's
+// lock) and hands out the device pointers, valid until the next add / select / reset / load.
+struct ShadowView {
+  const unsigned char* rows16 = nullptr;  // bf16 [n][dim], allocated to whole 32-row blocks
+  const unsigned* stats16 = nullptr;      // [0] max ||c - bf16(c)||, [1] max ||c|| (float bits)
+  int num_cus = 0;
+};
+int index_shadow(mq_index* ix, hipStream_t s, ShadowView* out);
+
 // ------------------------------------------------------------ device side ----
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));

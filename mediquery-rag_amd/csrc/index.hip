@@ -2139,6 +2139,17 @@ struct FileHeader {
 
 }  // namespace
 
+// common.hpp: the bf16 shadow for join.hip (K18), brought up to date on `s`.
+int mq::index_shadow(mq_index* ix, hipStream_t s, ShadowView* out) {
+  std::lock_guard<std::mutex> lk(ix->mu);
+  DeviceGuard dg(ix->device);
+  if (int rc = ensure_shadow(ix, s)) return rc;
+  out->rows16 = ix->rows16.as<unsigned char>();
+  out->stats16 = ix->stats16.as<unsigned>();
+  out->num_cus = ix->num_cus;
+  return MQ_OK;
+}
+
 extern "C" {
 
 int mq_index_create(int device, int dim, int64_t capacity, int dtype, mq_index** out) {

@@ -476,6 +476,37 @@ void launch_thresh(const ThreshArgs& a, hipStream_t s, Timeline* tl) {
     launch_dim<false>(a, s, tl);
 }
 
+// The appending pass alone with the caller's tau (join.hip, K18): count zeroed, then every row
+// block against a.tau.  The launch geometry is launch_nch's.
+template <int NCH, bool MASKED>
+void append_nch(const ThreshArgs& a, hipStream_t s) {
+  const int gy = (a.nq + kTsQ - 1) / kTsQ;
+  const int G = gy == 1 ? a.num_cus : std::max(8, a.num_cus / gy / 8 * 8);
+  const int64_t n_blocks = (a.n + kTsRows - 1) / kTsRows;
+  hipLaunchKernelGGL((bf16_thresh_kernel<NCH, TS_APPEND, MASKED>), dim3(G, gy), dim3(512), 0, s,
+                     reinterpret_cast<const uint4*>(a.q16), a.nq, a.rows, a.n, n_blocks, 1, a.tau, a.lmax, a.count,
+                     a.cs, a.ci, a.mask);
+}
+
+template <bool MASKED>
+void append_dim(const ThreshArgs& a, hipStream_t s) {
+  switch (a.dim / 64) {
+    case 4: append_nch<4, MASKED>(a, s); break;
+    case 8: append_nch<8, MASKED>(a, s); break;
+    default: append_nch<12, MASKED>(a, s); break;
+  }
+}
+
+hipError_t launch_thresh_append(const ThreshArgs& a, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(a.count, 0, (size_t)a.nq * sizeof(int), s);
+  if (e != hipSuccess) return e;
+  if (a.mask)
+    append_dim<true>(a, s);
+  else
+    append_dim<false>(a, s);
+  return hipGetLastError();
+}
+
 // ============================ K9q: int8 threshold scan (few-query screens) ==========
 // A single query (or up to 4) over the int8 shadow: a row is stored as int8 r8 with one
 // fp32 scale (absmax / 127), 1 byte per element - half the bytes of the bf16 shadow that

@@ -36,6 +36,11 @@ struct ThreshArgs {
 
 // Enqueue the four K9t launches on `s`; timeline stage 0 = the two scans, 1 = tau + select.
 void launch_thresh(const ThreshArgs& a, hipStream_t s, Timeline* tl);
+// The appending scan alone, with a tau the caller has filled (join.hip, K18): zeroes count[nq],
+// then every row block whose score clears tau[q] is appended to query q's survivors (cs / ci /
+// count; count keeps counting past kTsCap).  Reads q16, nq <= any multiple of 256, rows, n,
+// dim (256, 512 or 768), num_cus, tau and mask only.
+hipError_t launch_thresh_append(const ThreshArgs& a, hipStream_t s);
 
 // K9q: the int8 threshold scan for one query (single-query certified screen).
 #ifndef MQ_I8_WG

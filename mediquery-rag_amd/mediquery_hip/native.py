@@ -344,6 +344,83 @@ class FlatIndex:
                       _lib.ptr(out_counts), _lib.ptr(out_scores), _lib.ptr(out_ids), 1, _lib.ptr(scratch),
                       scratch.numel() * scratch.element_size(), _lib.stream_handle(stream))
 
+    def _join_args(self, bits, scratch, n_left, min_score, mode):
+        """The device checks of the self-join calls -> (min_score, mode, scratch)."""
+        import torch
+        n, min_score, mode = len(self), float(min_score), int(mode)
+        if min_score != min_score:
+            raise ValueError("min_score must not be NaN (-inf means no threshold)")
+        if mode not in (_lib.MQ_JOIN_AUTO, _lib.MQ_JOIN_EXACT, _lib.MQ_JOIN_SCREEN):
+            raise ValueError("mode must be MQ_JOIN_AUTO, MQ_JOIN_EXACT or MQ_JOIN_SCREEN (got %d)" % mode)
+        if self.dim % 64 or self.dim > 1024:
+            raise ValueError("the self-join serves dim %% 64 == 0, dim <= 1024 (got %d)" % self.dim)
+        if mode == _lib.MQ_JOIN_SCREEN and self.dim not in (256, 512, 768):
+            raise ValueError("MQ_JOIN_SCREEN serves dim 256, 512 or 768 (got %d)" % self.dim)
+        if bits is not None:
+            self._check_bits(bits)
+        need = join_scratch_bytes(n, n_left)
+        if scratch is None:
+            scratch = torch.empty(max(need, 256), dtype=torch.uint8, device=torch.device("cuda", int(self.device)))
+        if not (getattr(scratch, "is_cuda", False) and scratch.is_contiguous()
+                and scratch.device.index == int(self.device)
+                and scratch.numel() * scratch.element_size() >= need and scratch.data_ptr() % 16 == 0):
+            raise ValueError("scratch must be a contiguous 16-byte aligned tensor of >= %d bytes on cuda:%d"
+                             % (need, self.device))
+        return min_score, mode, scratch
+
+    def self_join(self, min_score, bits=None, left_rows=None, mode=_lib.MQ_JOIN_AUTO, scratch=None):
+        """Self-join (K18, mq_index_self_join): for every left row (left_rows: distinct row ids,
+        None = every row) its partners - the other rows `bits` admits (a row mask as for
+        search_masked; None = every row) whose exact fp32 score against it is >= min_score.
+        scratch: join_scratch_bytes(n, n_left) device bytes (None: a torch.empty of that size).
+        -> (counts int64, first int64, nearest int64, nearest_scores float32, info int64 [4]),
+        the first four [n_left]: the number of partners, the smallest partner row (-1: none),
+        the best partner by (score desc, row asc) and its score (-1, -inf: none); info = (sum of
+        the counts, left rows the screen answered, screen candidates verified, left rows the
+        exact walk answered).  The modes return the same four arrays."""
+        n = len(self)
+        if left_rows is not None:
+            left_rows = np.ascontiguousarray(left_rows, dtype=np.int64).reshape(-1)
+        n_left = n if left_rows is None else len(left_rows)
+        counts = np.empty(n_left, dtype=np.int64)
+        first = np.empty(n_left, dtype=np.int64)
+        nearest = np.empty(n_left, dtype=np.int64)
+        scores = np.empty(n_left, dtype=np.float32)
+        info = np.zeros(4, dtype=np.int64)
+        with _lib.device_scope(self.device):
+            min_score, mode, scratch = self._join_args(bits, scratch, n_left, min_score, mode)
+            _lib.call("mq_index_self_join", self._h, min_score, _lib.ptr(bits), _lib.ptr(left_rows), n_left, mode,
+                      _lib.ptr(counts), _lib.ptr(first), _lib.ptr(nearest), _lib.ptr(scores), _lib.ptr(info), 0,
+                      _lib.ptr(scratch), scratch.numel() * scratch.element_size(), _lib.stream_handle(None))
+        return counts, first, nearest, scores, info
+
+    def self_join_device(self, min_score, out_counts, out_first, out_nearest, out_nearest_scores, out_info, bits=None,
+                         left_rows=None, mode=_lib.MQ_JOIN_AUTO, scratch=None, stream=None):
+        """self_join on torch device tensors (left_rows int64 [n_left] or None, out_counts /
+        out_first / out_nearest int64 [n_left], out_nearest_scores float32 [n_left], out_info
+        int64 [4]) on the given (or current) torch stream, which the call synchronises."""
+        import torch
+        n_left = len(self) if left_rows is None else left_rows.numel()
+        for t, dt, cnt in ((left_rows, torch.int64, n_left), (out_counts, torch.int64, n_left),
+                           (out_first, torch.int64, n_left), (out_nearest, torch.int64, n_left),
+                           (out_nearest_scores, torch.float32, n_left), (out_info, torch.int64, 4)):
+            if t is left_rows and t is None:
+                continue
+            if not (getattr(t, "is_cuda", False) and t.dtype == dt and t.is_contiguous()
+                    and t.device.index == int(self.device) and t.numel() >= cnt):
+                raise ValueError("left_rows / out_counts / out_first / out_nearest / out_nearest_scores / out_info must "
+                                 "be contiguous int64 / int64 / int64 / int64 / float32 / int64 tensors of [n_left] "
+                                 "([4] for out_info) on cuda:%d" % self.device)
+        with _lib.device_scope(self.device):
+            min_score, mode, scratch = self._join_args(bits, scratch, n_left, min_score, mode)
+            if scratch.data_ptr() in (out_counts.data_ptr(), out_first.data_ptr(), out_nearest.data_ptr(),
+                                      out_nearest_scores.data_ptr(), out_info.data_ptr()):
+                raise ValueError("scratch must not be one of the outputs")
+            _lib.call("mq_index_self_join", self._h, min_score, _lib.ptr(bits), _lib.ptr(left_rows), n_left, mode,
+                      _lib.ptr(out_counts), _lib.ptr(out_first), _lib.ptr(out_nearest), _lib.ptr(out_nearest_scores),
+                      _lib.ptr(out_info), 1, _lib.ptr(scratch), scratch.numel() * scratch.element_size(),
+                      _lib.stream_handle(stream))
+
     @property
     def masked_gathers(self):
         """Masked searches the int8 screen did not certify (answered from gathered rows)."""
@@ -376,6 +453,12 @@ def range_scratch_bytes(n_rows, nq, max_hits=_lib.MQ_RANGE_MAX_HITS):
     """Bytes of device scratch mq_index_search_range wants for n_rows rows, nq queries and lists
     of max_hits; non-decreasing in every argument and bounded in nq."""
     return int(_lib.lib().mq_range_scratch_bytes(int(n_rows), int(nq), int(max_hits)))
+
+
+def join_scratch_bytes(n_rows, n_left):
+    """Bytes of device scratch mq_index_self_join wants for n_rows rows and n_left left rows;
+    non-decreasing in both."""
+    return int(_lib.lib().mq_join_scratch_bytes(int(n_rows), int(n_left)))
 
 
 def range_scan_blocks(n_rows, compute_units):

@@ -48,6 +48,15 @@ always in exact fp32.  `similarity_search_with_relevance_scores(score_threshold=
 ordinary top-k the way LangChain's base class does, and `as_retriever` takes
 `search_type="similarity_score_threshold"` and `"range"`.
 
+Near-duplicate detection (LangChain's `EmbeddingsRedundantFilter`, at the scale of the store):
+`duplicate_scan` asks the index about itself - for every row, or the rows of `ids`, how many other
+rows have a cosine to it of at least `min_cosine`, which is the smallest and which the nearest - in
+one device self-join (mq_index_self_join, the definition: include/mq.h "Self-join"; a bf16 MFMA
+screen with a proven bound, its survivors verified in the range search's exact fp32 arithmetic, or
+the exact walk alone: `mode`).  `deduplicate` deletes the rows the sequential greedy rule drops (a
+row is kept iff no kept earlier row is its partner; `greedy_dedup_rounds`), `find_duplicates`
+lists them with the kept row that makes each redundant.  All take `filter` and `where_document`.
+
 Persistence: `mq_<collection>.json` (ids, documents, metadatas, and the name of the slab
 file) is the base commit point; a full write (the first write, `delete`, an upsert that
 replaces rows, an explicit `persist()`) puts the rows in a fresh `mq_<collection>.<gen>.flat`
@@ -73,7 +82,7 @@ import numpy as np
 
 from . import _lib
 from .compat import Document, VectorStoreBase
-from .native import (FlatIndex, group_scratch_bytes, lex_batch_scratch_bytes, lex_df, lex_df_batch,
+from .native import (FlatIndex, group_scratch_bytes, join_scratch_bytes, lex_batch_scratch_bytes, lex_df, lex_df_batch,
                      lex_scratch_bytes, lex_topk, lex_topk_batch, mask_combine, mask_contains, mask_eval,
                      mask_eval_bits, range_scratch_bytes)
 
@@ -653,6 +662,77 @@ def _check_min_cosine(min_cosine):
     return float(min_cosine)
 
 
+def _check_dup_cosine(min_cosine):
+    """The threshold of the duplicate scans: a finite number (None is refused: every row would
+    be every row's partner)."""
+    if min_cosine is None:
+        raise ValueError("min_cosine must be a finite number, got None")
+    return _check_min_cosine(min_cosine)
+
+
+JOIN_MODES = {"auto": _lib.MQ_JOIN_AUTO, "exact": _lib.MQ_JOIN_EXACT, "screen": _lib.MQ_JOIN_SCREEN}
+
+
+class DuplicateScan:
+    """What `HipChroma.duplicate_scan` returns, host arrays of one entry per left row: `rows`
+    (the left rows, ascending), `counts` (partners: other admitted rows at or above the
+    threshold), `first` (the smallest partner row, -1: none), `nearest` / `nearest_cosine` (the
+    partner of the highest cosine, ties to the lowest row; -1 / -inf: none), and `info`
+    (mq_index_self_join's out_info)."""
+
+    def __init__(self, rows, counts, first, nearest, nearest_cosine, info):
+        self.rows, self.counts, self.first = rows, counts, first
+        self.nearest, self.nearest_cosine, self.info = nearest, nearest_cosine, info
+
+    def __len__(self):
+        return len(self.rows)
+
+
+class DedupResult(list):
+    """What `deduplicate` (deleted ids) and `find_duplicates` (triples) return: a list with
+    `undecided`, the ids still undecided after max_rounds (they are kept), and `rounds`, the
+    scans that ran."""
+
+    def __init__(self, items=(), undecided=(), rounds=0):
+        super().__init__(items)
+        self.undecided, self.rounds = list(undecided), int(rounds)
+
+
+def greedy_dedup_rounds(n, left, admitted, scan_first, max_rounds=32):
+    """The sequential greedy rule - a left row is kept iff no KEPT earlier row is its partner -
+    computed in rounds of whole scans.  left: the rows that may be dropped (ascending, distinct);
+    admitted: bool [n], the rows that take part (a left row outside it is kept untouched); every
+    admitted row outside `left` is kept.  scan_first(rows, mask) -> for each of `rows` its
+    smallest partner among the rows of the bool mask [n], or -1.
+    Each round scans the undecided rows under the mask of the kept and undecided rows and walks
+    them in ascending order: no earlier partner (first < 0 or first > row) -> kept; `first` is a
+    kept row -> dropped, with `first` as its keeper; otherwise (first is undecided, or was
+    dropped in this round, so another earlier partner may remain) the row waits for the next
+    round, whose mask leaves the dropped rows out.  The smallest undecided row is always decided
+    (every earlier row of the mask is kept), so the rounds end.
+    -> (dropped rows ascending, their keepers, undecided rows after max_rounds, rounds run)."""
+    KEPT, UNDECIDED, DROPPED = 0, 1, 2
+    admitted = np.asarray(admitted, bool)
+    state = np.full(n, KEPT, np.int8)
+    left = np.asarray(left, np.int64)
+    left = left[admitted[left]] if len(left) else left
+    state[left] = UNDECIDED
+    keeper = {}
+    undecided, rounds = left, 0
+    while len(undecided) and rounds < max_rounds:
+        rounds += 1
+        first = scan_first(undecided, admitted & (state != DROPPED))
+        for r, f in zip(undecided.tolist(), np.asarray(first).tolist()):
+            if f < 0 or f > r:
+                state[r] = KEPT
+            elif state[f] == KEPT:
+                state[r] = DROPPED
+                keeper[r] = f
+        undecided = undecided[state[undecided] == UNDECIDED]
+    dropped = np.array(sorted(keeper), np.int64)
+    return dropped, np.array([keeper[r] for r in dropped.tolist()], np.int64), undecided, rounds
+
+
 def _check_score_threshold(score_threshold):
     if isinstance(score_threshold, bool) or not isinstance(score_threshold, (int, float, np.integer, np.floating)) \
             or math.isnan(score_threshold):
@@ -796,6 +876,7 @@ class HipChroma(VectorStoreBase):
         self._group_scratch = None     # the group scan's device scratch, grown on demand
         self._group_absent = None      # ((key, codes version), some row lacks the key)
         self._range_scratch = None     # the range search's device scratch, grown on demand
+        self._join_scratch = None      # the self-join's device scratch, grown on demand
         if search_precision not in SEARCH_PRECISIONS:
             raise ValueError("search_precision must be one of %s, got %r"
                              % (sorted(SEARCH_PRECISIONS), search_precision))
@@ -1471,6 +1552,116 @@ class HipChroma(VectorStoreBase):
         if self._index is None or len(self._index) == 0:
             return 0
         return self.count_similar_by_vector(self._embed_query(query), min_cosine, filter, where_document)
+
+    # ---- near-duplicate detection: the self-join of the store ------------------------------
+    def _join_room(self, n, n_left):
+        """The self-join's scratch: grows on demand and is kept."""
+        import torch
+        need = join_scratch_bytes(n, n_left)
+        if self._join_scratch is None or self._join_scratch.numel() < need:
+            self._join_scratch = None  # release before growing
+            with _lib.device_scope(self._device):
+                self._join_scratch = torch.empty(need, dtype=torch.uint8, device=torch.device("cuda", self._device))
+        return self._join_scratch
+
+    def _host_bits(self, mask):
+        """bool [n] -> a device row mask in the masked search's layout."""
+        import torch
+        padded = np.zeros((len(mask) + 31) // 32 * 32 or 32, np.uint8)
+        padded[:len(mask)] = mask
+        words = np.packbits(padded, bitorder="little").view(np.int32)
+        return torch.from_numpy(words).to(torch.device("cuda", self._device))
+
+    def _dup_setup(self, min_cosine, ids, filter, where_document, mode):
+        """The checks the duplicate calls share -> (min_score, mode, left rows ascending or None
+        for every row, device mask or None)."""
+        if where_document is not None:
+            _check_where_document(where_document)
+        min_score = _check_dup_cosine(min_cosine)
+        if mode not in JOIN_MODES:
+            raise ValueError("mode must be one of %s, got %r" % (sorted(JOIN_MODES), mode))
+        n = 0 if self._index is None else len(self._index)
+        if n and (self._dim % 64 or self._dim > 1024):
+            raise ValueError("the duplicate scan serves stores of dim %% 64 == 0, dim <= 1024 (this store's dim is %d)"
+                             % self._dim)
+        if mode == "screen" and n and self._dim not in (256, 512, 768):
+            raise ValueError("mode='screen' serves stores of dim 256, 512 or 768 (this store's dim is %d)" % self._dim)
+        left = None
+        if ids is not None:
+            want = [ids] if isinstance(ids, str) else ids
+            left = np.array(sorted({self._id_row.row(str(i)) for i in want if str(i) in self._id_row}), np.int64)
+        bits = None
+        if n and (filter or where_document is not None):
+            _, bits = self._admit(1, filter, where_document)
+        return min_score, JOIN_MODES[mode], left, bits
+
+    def duplicate_scan(self, min_cosine=0.95, ids=None, filter=None, where_document=None, mode="auto"):
+        """Which rows are near-copies of other rows: for every left row (`ids`: those documents,
+        for example the ids `add_texts` just returned; None: every row) the number of its
+        partners - the other rows `filter` / `where_document` admit whose cosine to it is >=
+        min_cosine (in fp32, the range search's arithmetic) - the smallest partner row and the
+        nearest partner, as a `DuplicateScan` of host arrays.  A left row the filters do not admit
+        has no partner.  One mq_index_self_join call (include/mq.h, "Self-join"); mode "auto",
+        "exact" or "screen" picks its path, never its answer."""
+        min_score, jmode, left, bits = self._dup_setup(min_cosine, ids, filter, where_document, mode)
+        n = 0 if self._index is None else len(self._index)
+        rows = np.arange(n, dtype=np.int64) if left is None else left
+        if n == 0 or not len(rows):
+            e = np.empty(0, np.int64)
+            return DuplicateScan(e, e.copy(), e.copy(), e.copy(), np.empty(0, np.float32), np.zeros(4, np.int64))
+        c, f, nn, s, info = self._index.self_join(min_score, bits, left, jmode, self._join_room(n, len(rows)))
+        return DuplicateScan(rows, c, f, nn, s, info)
+
+    def _dedup_plan(self, min_cosine, ids, filter, where_document, mode, max_rounds):
+        """-> (dropped rows, their keepers, undecided rows, rounds) of `greedy_dedup_rounds` over
+        the store, each round one mq_index_self_join of the undecided rows."""
+        if isinstance(max_rounds, bool) or not isinstance(max_rounds, (int, np.integer)) or max_rounds < 1:
+            raise ValueError("max_rounds must be a positive integer, got %r" % (max_rounds,))
+        min_score, jmode, left, bits = self._dup_setup(min_cosine, ids, filter, where_document, mode)
+        n = 0 if self._index is None else len(self._index)
+        e = np.empty(0, np.int64)
+        if n == 0 or (left is not None and not len(left)):
+            return e, e, e, 0
+        admitted = np.ones(n, bool) if bits is None else self._mask_rows(bits)
+        whole = [bits is None]  # the first round of an unfiltered store needs no mask at all
+
+        def scan_first(rows, mask):
+            dbits = None if whole[0] and mask.all() else self._host_bits(mask)
+            whole[0] = False
+            return self._index.self_join(min_score, dbits, rows, jmode, self._join_room(n, len(rows)))[1]
+
+        return greedy_dedup_rounds(n, np.arange(n, dtype=np.int64) if left is None else left, admitted, scan_first,
+                                   int(max_rounds))
+
+    def find_duplicates(self, min_cosine=0.95, ids=None, filter=None, where_document=None, mode="auto",
+                        max_rounds=32):
+        """[(Document, kept Document, cosine)] for every row `deduplicate` would drop with the
+        same arguments: the document, the earlier kept document that makes it redundant (the
+        smallest such row) and their cosine.  Deletes nothing."""
+        dropped, keepers, undecided, rounds = self._dedup_plan(min_cosine, ids, filter, where_document, mode,
+                                                               max_rounds)
+        out = DedupResult((), [self._ids[r] for r in undecided.tolist()], rounds)
+        if len(dropped):
+            pairs = self._index.select(np.concatenate([dropped, keepers])).get().astype(np.float64)
+            cos = (pairs[:len(dropped)] * pairs[len(dropped):]).sum(1)
+            out.extend((self._doc(r), self._doc(k), float(c))
+                       for r, k, c in zip(dropped.tolist(), keepers.tolist(), cos.tolist()))
+        return out
+
+    def deduplicate(self, min_cosine=0.95, ids=None, filter=None, where_document=None, mode="auto", max_rounds=32):
+        """Delete the near-copies and return their ids (a `DedupResult`).  A row is kept iff no
+        KEPT earlier row is its partner (cosine >= min_cosine, both admitted by the filters): the
+        sequential greedy rule in insertion order, well defined although "near" is not
+        transitive.  `ids` limits the rows that may be dropped (for example to the ids
+        `add_texts` just returned; every other row is kept and still makes later copies of it
+        redundant).  Computed in rounds of whole device scans (`greedy_dedup_rounds`); rows still
+        undecided after max_rounds are kept and listed in the result's `undecided`."""
+        dropped, _, undecided, rounds = self._dedup_plan(min_cosine, ids, filter, where_document, mode, max_rounds)
+        gone = [self._ids[r] for r in dropped.tolist()]
+        out = DedupResult(gone, [self._ids[r] for r in undecided.tolist()], rounds)
+        if gone:
+            self.delete(gone)
+        return out
 
     # ---- lexical (BM25) and hybrid (reciprocal rank fusion) retrieval ----------------------
     def _lex_tok(self):
