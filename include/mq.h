@@ -546,6 +546,75 @@ int mq_debug_join_check(int dim, int64_t n_rows, float min_score, int mode, cons
                         const float* out_nearest_scores, const int64_t* out_info, const void* scratch,
                         int64_t scratch_bytes);
 
+/* K-means (K19; LangChain's EmbeddingsClusteringFilter at index scale: the themes of a corpus
+ * and a representative of each): Lloyd iterations over the stored rows, on the device.
+ * Inputs: the index rows; an optional device row mask `bits` in the layout of the masked search
+ * (NULL: every row) - a row is admitted when the mask admits it; n_clusters in
+ * [1, MQ_KMEANS_MAX_CLUSTERS] centroids, centroids float [n_clusters, dim], read and
+ * overwritten; n_iter in [0, 1024].
+ * Score: score(c, r) is the chain of csrc/score_chain.hpp exactly - chain_step over the 16-byte
+ * pieces `it` ascending, then chain_reduce16 - with centroid c as the vector in LDS and stored
+ * row r from the slab: the arithmetic of the range search and the self-join.  (The chain starts
+ * from +0, so a score is never -0.0.)  half_j = 0.5f * score(c_j, c_j), computed by the same
+ * chain once per set of centroids and kept in memory.  d_j(r) = (score(c_j, r) - half_j) + 0.0f,
+ * a plain fp32 subtraction of two stored values.  For unit rows |r - c_j|^2 = |r|^2 - 2 d_j(r),
+ * so the largest d is the Euclidean nearest centre: what sklearn's KMeans assigns to.
+ * assign(C): an admitted row gets a[r] = argmax_j d_j(r), equal d to the lowest j - the order of
+ * the keys chain_key(chain_score_word(d), j) - and out_dots[r] = score(c_a[r], r); any other row
+ * gets a[r] = -1 and out_dots[r] = -inf.
+ * update(a, C): counts[j] = #{r : a[r] = j}; a cluster with counts[j] > 0 gets, per coordinate,
+ * c_j = S_j / (float)counts[j], S_j the fp32 sum of its members' coordinate and the division one
+ * IEEE fp32 division (__fdiv_rn); an empty cluster keeps its centroid bit for bit.  The order of
+ * the sum is fixed by (n, n_clusters, the labels): the rows are cut into chunks (at least 256
+ * rows each, at most min(1024, 8192 / n_clusters) of them), a chunk's members of a cluster are
+ * added in ascending row order and the chunks' sums in ascending chunk order.  No floating-point
+ * atomics; repeated calls return the same bits.
+ * The call: a_0 = assign(C_0); for t = 0 .. n_iter - 1: C_{t+1} = update(a_t, C_t), a_{t+1} =
+ * assign(C_{t+1}).  It writes C_{n_iter} back into `centroids` and a_{n_iter}, its dots and its
+ * counts to out_assign int32 [n], out_dots float [n], out_counts int64 [n_clusters]: labels,
+ * counts and centroids are always consistent with each other, and n_iter = 0 is a pure predict.
+ * Convergence: with changed_t = #{r : a_t[r] != a_{t-1}[r]} (a_{-1} = -1 everywhere), once some
+ * changed_t = 0 every later step would reproduce the same bits, and the later launches return at
+ * once on a device flag.  They are still enqueued: nothing is read back during the call and the
+ * number of launches is a function of (n_clusters, n_iter) alone.
+ * out_info int64 [4]: [0] updates applied before convergence, [1] `changed` at the last assign
+ * that ran (0: converged), [2] admitted rows, [3] empty clusters at the end.
+ * An empty index or an all-zero mask: every label -1, every count 0, the centroids untouched.
+ * n_clusters may exceed the admitted rows; the surplus clusters stay empty.
+ *
+ * kmeans_half_kernel computes the halves, one 16-lane group per centroid.  kmeans_assign_kernel
+ * is range_score_kernel's row walk (16 lanes per row, non-temporal 16-byte loads, two rows in
+ * flight, mq_range_scan_blocks(n, CUs) workgroups) over the centroids in passes of 16; the lane
+ * that owns (row, j) forms the key, a row's running best key lives in a uint64 [n] array of the
+ * scratch between passes and the winner's score in out_dots, each written by the row's one lane
+ * group; the last pass writes the label and counts `changed`, one integer atomic per wave.
+ * kmeans_partial_kernel (grid: chunk x cluster) compacts a chunk's members in row order and adds
+ * their rows, each thread owning four coordinates; kmeans_finish_kernel folds the chunks, divides
+ * and writes the centroid.  Every hand-off is a kernel boundary on one stream.
+ *
+ * centroids and the four outputs are all host (io_on_device = 0: staged through the scratch, the
+ * call synchronises) or all device (asynchronous on `stream`); bits and scratch are device
+ * memory of the index's GPU.  Checked before any HIP call, each with a message naming the
+ * offending value: n_clusters and n_iter (both before the handle is looked at), dim % 64 == 0 and
+ * dim <= 1024, n < 2^31, non-NULL buffers, scratch 16-byte aligned, at least
+ * mq_kmeans_scratch_bytes(n, n_clusters) bytes and overlapping no other buffer, host centroids
+ * all finite.  Device centroids that are not finite give unspecified labels in [0, n_clusters)
+ * and write nothing out of bounds.  The call allocates no device memory and reads the slab as it
+ * stood when the call began.
+ * mq_kmeans_scratch_bytes is non-decreasing in both arguments (a multiple of 256; arguments out
+ * of range are clamped): 16 bytes per row (the best keys and a host call's staged labels and
+ * dots), the update's partial sums (4 KB for each of at most min(n_clusters x min(1024,
+ * ceil(n / 256)), 8192) cluster chunks: 32 MB at most) and 4 KB of staging per centroid.
+ * mq_debug_kmeans_check runs the HIP-free checks alone on a stated index shape (dim, n_rows). */
+#define MQ_KMEANS_MAX_CLUSTERS 256
+int64_t mq_kmeans_scratch_bytes(int64_t n_rows, int n_clusters);
+int mq_index_kmeans(mq_index* ix, const uint32_t* bits, int n_clusters, int n_iter, float* centroids,
+                    int32_t* out_assign, float* out_dots, int64_t* out_counts, int64_t* out_info, int io_on_device,
+                    void* scratch, int64_t scratch_bytes, void* stream);
+int mq_debug_kmeans_check(int dim, int64_t n_rows, int n_clusters, int n_iter, const float* centroids,
+                          const int32_t* out_assign, const float* out_dots, const int64_t* out_counts,
+                          const int64_t* out_info, int io_on_device, const void* scratch, int64_t scratch_bytes);
+
 /* Persistence: a flat binary slab (header + rows); written files are
  * fsync'ed before the call returns. */
 int mq_index_save(mq_index* ix, const char* path);

@@ -14,7 +14,7 @@ from .compat import Document, HAVE_LANGCHAIN
 from ._lib import MQError, MQ_MAX_K, MQ_RANGE_MAX_HITS, device_count, lib
 from .native import Encoder, FlatIndex, merge_topk_device, merge_topk_host
 from .embeddings import HipBertEmbeddings
-from .vectorstore import DedupResult, DuplicateScan, HipChroma, RangeResult
+from .vectorstore import ClusterResult, DedupResult, DuplicateScan, HipChroma, RangeResult
 from .cross_encoder import HipCrossEncoder, HipReranker
 from .parent_retriever import HipParentDocumentRetriever, WindowSplitter
 
@@ -23,8 +23,8 @@ OllamaEmbeddings = HipBertEmbeddings
 Chroma = HipChroma
 
 __all__ = ["BertConfig", "DMETA_BASE", "GELU_ERF", "GELU_TANH", "POOL_CLS", "POOL_MEAN",
-           "DedupResult", "Document", "DuplicateScan", "HAVE_LANGCHAIN", "MQError", "MQ_MAX_K", "MQ_RANGE_MAX_HITS",
-           "device_count", "lib",
+           "ClusterResult", "DedupResult", "Document", "DuplicateScan", "HAVE_LANGCHAIN", "MQError", "MQ_MAX_K",
+           "MQ_RANGE_MAX_HITS", "device_count", "lib",
            "Encoder",
            "FlatIndex", "merge_topk_device", "merge_topk_host", "HipBertEmbeddings", "HipChroma",
            "OllamaEmbeddings", "Chroma", "HipCrossEncoder", "HipReranker",

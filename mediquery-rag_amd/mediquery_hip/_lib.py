@@ -24,6 +24,7 @@ MQ_MAX_K = 64
 MQ_RANGE_MAX_HITS = 4096         # longest list of mq_index_search_range (its count is not bounded)
 MQ_HEAD_MAX_LABELS = 8           # most labels a cross-encoder head carries (mq_encoder_load_head)
 MQ_JOIN_AUTO, MQ_JOIN_EXACT, MQ_JOIN_SCREEN = 0, 1, 2   # mq_index_self_join modes
+MQ_KMEANS_MAX_CLUSTERS = 256     # most centroids one mq_index_kmeans call takes
 MQ_MASK_SET, MQ_MASK_AND, MQ_MASK_OR, MQ_MASK_CLEAR = 0, 1, 2, 3
 MQ_CONTAINS_MAX_BYTES = 256      # longest mq_mask_contains pattern (UTF-8 bytes)
 MQ_CONTAINS_SPAN_BYTES = 16384   # text bytes one workgroup of the scan owns
@@ -128,6 +129,9 @@ SIGNATURES = {
     "mq_join_scratch_bytes": (_I64, [_I64, _I64]),
     "mq_index_self_join": (_I, [_P, ctypes.c_float, _P, _P, _I64, _I, _P, _P, _P, _P, _P, _I, _P, _I64, _P]),
     "mq_debug_join_check": (_I, [_I, _I64, ctypes.c_float, _I, _P, _I64, _P, _P, _P, _P, _P, _P, _I64]),
+    "mq_kmeans_scratch_bytes": (_I64, [_I64, _I]),
+    "mq_index_kmeans": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _I64, _P]),
+    "mq_debug_kmeans_check": (_I, [_I, _I64, _I, _I, _P, _P, _P, _P, _P, _I, _P, _I64]),
     "mq_topk_merge_host": (_I, [_P, _P, _I, _I64, _I, _I, _P, _P]),
     "mq_topk_merge_device": (_I, [_P, _P, _I, _I64, _I, _I, _P, _P, _P]),
     "mq_encoder_create": (_I, [_I, ctypes.POINTER(BertConfigC), _PP]),

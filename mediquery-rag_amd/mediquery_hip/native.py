@@ -421,6 +421,81 @@ class FlatIndex:
                       _lib.ptr(out_info), 1, _lib.ptr(scratch), scratch.numel() * scratch.element_size(),
                       _lib.stream_handle(stream))
 
+    def _kmeans_args(self, bits, scratch, n_clusters, n_iter):
+        """The device checks of the k-means calls -> (n_iter, scratch)."""
+        import torch
+        n, n_iter = len(self), int(n_iter)
+        if not 1 <= n_clusters <= _lib.MQ_KMEANS_MAX_CLUSTERS:
+            raise ValueError("n_clusters must be in [1, %d] (got %d)" % (_lib.MQ_KMEANS_MAX_CLUSTERS, n_clusters))
+        if not 0 <= n_iter <= 1024:
+            raise ValueError("n_iter must be in [0, 1024] (got %d)" % n_iter)
+        if self.dim % 64 or self.dim > 1024:
+            raise ValueError("k-means serves dim %% 64 == 0, dim <= 1024 (got %d)" % self.dim)
+        if bits is not None:
+            self._check_bits(bits)
+        need = kmeans_scratch_bytes(n, n_clusters)
+        if scratch is None:
+            scratch = torch.empty(max(need, 256), dtype=torch.uint8, device=torch.device("cuda", int(self.device)))
+        if not (getattr(scratch, "is_cuda", False) and scratch.is_contiguous()
+                and scratch.device.index == int(self.device)
+                and scratch.numel() * scratch.element_size() >= need and scratch.data_ptr() % 16 == 0):
+            raise ValueError("scratch must be a contiguous 16-byte aligned tensor of >= %d bytes on cuda:%d"
+                             % (need, self.device))
+        return n_iter, scratch
+
+    def kmeans(self, centroids, n_iter, bits=None, scratch=None):
+        """K-means (K19, mq_index_kmeans): n_iter Lloyd iterations from `centroids`
+        [n_clusters, dim] (all finite; not modified) over the rows `bits` admits (a row mask as for
+        search_masked; None = every row); n_iter = 0 only labels the rows.  scratch:
+        kmeans_scratch_bytes(n, n_clusters) device bytes (None: a torch.empty of that size).
+        -> (centroids float32 [n_clusters, dim], assign int32 [n], dots float32 [n], counts int64
+        [n_clusters], info int64 [4]): the final centres, each row's cluster (-1: not admitted),
+        its exact fp32 dot with that centre (-inf: not admitted), the cluster sizes, and info =
+        (updates applied before convergence, labels changed by the last assign that ran - 0 means
+        converged -, admitted rows, empty clusters)."""
+        c = np.array(centroids, dtype=np.float32, order="C")  # a copy: the call overwrites it
+        if c.ndim != 2 or c.shape[1] != self.dim:
+            raise ValueError("centroids must be [n_clusters, %d] (got shape %r)" % (self.dim, c.shape))
+        if not np.isfinite(c).all():
+            raise ValueError("centroids must be finite")
+        n = len(self)
+        assign = np.full(n, -1, dtype=np.int32)
+        dots = np.full(n, -np.inf, dtype=np.float32)
+        counts = np.zeros(c.shape[0], dtype=np.int64)
+        info = np.zeros(4, dtype=np.int64)
+        with _lib.device_scope(self.device):
+            n_iter, scratch = self._kmeans_args(bits, scratch, c.shape[0], n_iter)
+            _lib.call("mq_index_kmeans", self._h, _lib.ptr(bits), c.shape[0], n_iter, _lib.ptr(c), _lib.ptr(assign),
+                      _lib.ptr(dots), _lib.ptr(counts), _lib.ptr(info), 0, _lib.ptr(scratch),
+                      scratch.numel() * scratch.element_size(), _lib.stream_handle(None))
+        return c, assign, dots, counts, info
+
+    def kmeans_device(self, centroids, n_iter, out_assign, out_dots, out_counts, out_info, bits=None, scratch=None,
+                      stream=None):
+        """kmeans on torch device tensors (centroids float32 [n_clusters, dim], updated in place;
+        out_assign int32 [n], out_dots float32 [n], out_counts int64 [n_clusters], out_info int64
+        [4]), asynchronous on the given (or current) torch stream."""
+        import torch
+        n = len(self)
+        if getattr(centroids, "ndim", 0) != 2 or centroids.shape[1] != self.dim:
+            raise ValueError("centroids must be [n_clusters, %d]" % self.dim)
+        nc = centroids.shape[0]
+        for t, dt, cnt in ((centroids, torch.float32, nc * self.dim), (out_assign, torch.int32, n),
+                           (out_dots, torch.float32, n), (out_counts, torch.int64, nc), (out_info, torch.int64, 4)):
+            if not (getattr(t, "is_cuda", False) and t.dtype == dt and t.is_contiguous()
+                    and t.device.index == int(self.device) and t.numel() >= cnt):
+                raise ValueError("centroids / out_assign / out_dots / out_counts / out_info must be contiguous float32 "
+                                 "/ int32 / float32 / int64 / int64 tensors of [n_clusters, dim] / [n] / [n] / "
+                                 "[n_clusters] / [4] on cuda:%d" % self.device)
+        with _lib.device_scope(self.device):
+            n_iter, scratch = self._kmeans_args(bits, scratch, nc, n_iter)
+            if scratch.data_ptr() in (centroids.data_ptr(), out_assign.data_ptr(), out_dots.data_ptr(),
+                                      out_counts.data_ptr(), out_info.data_ptr()):
+                raise ValueError("scratch must not be one of the buffers")
+            _lib.call("mq_index_kmeans", self._h, _lib.ptr(bits), nc, n_iter, _lib.ptr(centroids),
+                      _lib.ptr(out_assign), _lib.ptr(out_dots), _lib.ptr(out_counts), _lib.ptr(out_info), 1,
+                      _lib.ptr(scratch), scratch.numel() * scratch.element_size(), _lib.stream_handle(stream))
+
     @property
     def masked_gathers(self):
         """Masked searches the int8 screen did not certify (answered from gathered rows)."""
@@ -459,6 +534,12 @@ def join_scratch_bytes(n_rows, n_left):
     """Bytes of device scratch mq_index_self_join wants for n_rows rows and n_left left rows;
     non-decreasing in both."""
     return int(_lib.lib().mq_join_scratch_bytes(int(n_rows), int(n_left)))
+
+
+def kmeans_scratch_bytes(n_rows, n_clusters=_lib.MQ_KMEANS_MAX_CLUSTERS):
+    """Bytes of device scratch mq_index_kmeans wants for n_rows rows and n_clusters centroids;
+    non-decreasing in both."""
+    return int(_lib.lib().mq_kmeans_scratch_bytes(int(n_rows), int(max(-1, min(int(n_clusters), 1 << 30)))))
 
 
 def range_scan_blocks(n_rows, compute_units):

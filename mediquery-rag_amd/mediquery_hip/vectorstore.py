@@ -57,6 +57,14 @@ the exact walk alone: `mode`).  `deduplicate` deletes the rows the sequential gr
 row is kept iff no kept earlier row is its partner; `greedy_dedup_rounds`), `find_duplicates`
 lists them with the kept row that makes each redundant.  All take `filter` and `where_document`.
 
+Clustering (LangChain's `EmbeddingsClusteringFilter`, at the scale of the store): `cluster` runs
+k-means over the rows - all of them, those the filters admit, or those of `ids`, such as a range
+search's hits - as Lloyd iterations on the device in the range search's exact fp32 arithmetic, with
+a deterministic sum (mq_index_kmeans, the definition: include/mq.h "K-means"), seeded by
+k-means++ (`kmeanspp_rows`), random rows or given centres, and returns a `ClusterResult`;
+`cluster_representatives` returns the documents nearest each centre by LangChain's rule
+(`pick_representatives`), ranked by one range search with the centres as queries.
+
 Persistence: `mq_<collection>.json` (ids, documents, metadatas, and the name of the slab
 file) is the base commit point; a full write (the first write, `delete`, an upsert that
 replaces rows, an explicit `persist()`) puts the rows in a fresh `mq_<collection>.<gen>.flat`
@@ -82,7 +90,8 @@ import numpy as np
 
 from . import _lib
 from .compat import Document, VectorStoreBase
-from .native import (FlatIndex, group_scratch_bytes, join_scratch_bytes, lex_batch_scratch_bytes, lex_df, lex_df_batch,
+from .native import (FlatIndex, group_scratch_bytes, join_scratch_bytes, kmeans_scratch_bytes,
+                     lex_batch_scratch_bytes, lex_df, lex_df_batch,
                      lex_scratch_bytes, lex_topk, lex_topk_batch, mask_combine, mask_contains, mask_eval,
                      mask_eval_bits, range_scratch_bytes)
 
@@ -733,6 +742,93 @@ def greedy_dedup_rounds(n, left, admitted, scan_first, max_rounds=32):
     return dropped, np.array([keeper[r] for r in dropped.tolist()], np.int64), undecided, rounds
 
 
+class ClusterResult:
+    """What `HipChroma.cluster` returns: `ids` (the admitted documents, in row order) and `labels`
+    (int32, each one's cluster), `centroids` (float32 [n_clusters, dim]), `counts` (int64, the
+    cluster sizes; 0: an empty cluster, whose centroid is its initial one), `iterations` (updates
+    applied before the labels stopped changing), `converged` (they did stop within max_iter) and
+    `inertia` (float64: the sum over the admitted rows of 1 - 2 dot + |c|^2, their squared
+    distance to their centre, rows taken as unit)."""
+
+    def __init__(self, ids, labels, centroids, counts, iterations, converged, inertia):
+        self.ids, self.labels, self.centroids, self.counts = ids, labels, centroids, counts
+        self.iterations, self.converged, self.inertia = int(iterations), bool(converged), float(inertia)
+
+    def __len__(self):
+        return len(self.ids)
+
+
+def kmeanspp_rows(n_admitted_rows, n_clusters, rng, dots_of_row):
+    """k-means++ seeding (D^2 sampling) over n_admitted_rows unit rows -> n_clusters distinct
+    positions (int64, in the order drawn).  dots_of_row(p) -> the dots of row p with every row
+    [n_admitted_rows]; the squared distance to p is 2 - 2 dot, clipped at 0.  The first seed is
+    rng.integers(n); each further one is rng.choice(n, p = m / sum(m)), m the running minimum of
+    the squared distances to the seeds so far (0 at the seeds themselves: no repeats); when every
+    remaining row coincides with a seed (sum(m) = 0) it is rng.choice of the rows not yet drawn."""
+    n, k = int(n_admitted_rows), int(n_clusters)
+    if not 1 <= k <= n:
+        raise ValueError("n_clusters %d needs at least as many rows (got %d)" % (k, n))
+    first = int(rng.integers(n))
+    picked = [first]
+    m = np.clip(2.0 - 2.0 * np.asarray(dots_of_row(first), np.float64), 0.0, None)
+    m[first] = 0.0
+    while len(picked) < k:
+        total = m.sum()
+        if total > 0.0:
+            nxt = int(rng.choice(n, p=m / total))
+        else:
+            free = np.ones(n, bool)
+            free[picked] = False
+            nxt = int(rng.choice(np.flatnonzero(free)))
+        picked.append(nxt)
+        m = np.minimum(m, np.clip(2.0 - 2.0 * np.asarray(dots_of_row(nxt), np.float64), 0.0, None))
+        m[picked] = 0.0
+    return np.array(picked, np.int64)
+
+
+def pick_representatives(ranked_lists, num_closest, remove_duplicates=False, sorted=False):
+    """LangChain's `EmbeddingsClusteringFilter` selection.  ranked_lists[j]: the rows ranked by
+    nearness to centre j, nearest first (at least the first n_clusters x num_closest of them, or
+    all).  Walk the clusters in order.  With remove_duplicates: take the first num_closest of
+    the ranking and drop those already taken.  Without it: take the first num_closest of the
+    ranking that are not already taken.  -> the rows in pick order, or ascending when `sorted`."""
+    taken, seen = [], set()
+    for ranking in ranked_lists:
+        ranking = [int(r) for r in ranking]
+        if remove_duplicates:
+            new = [r for r in ranking[:num_closest] if r not in seen]
+        else:
+            new = [r for r in ranking if r not in seen][:num_closest]
+        taken.extend(new)
+        seen.update(new)
+    if sorted:
+        taken.sort()
+    return taken
+
+
+CLUSTER_INITS = ("k-means++", "random")
+
+
+def _check_cluster_args(n_clusters, max_iter, init, seed, dim):
+    """-> (n_clusters, max_iter, init): init a name of CLUSTER_INITS or a float32 [n_clusters, dim]."""
+    for name, v, lo, hi in (("n_clusters", n_clusters, 1, _lib.MQ_KMEANS_MAX_CLUSTERS), ("max_iter", max_iter, 0, 1024)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, hi, v))
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
+        raise ValueError("seed must be a non-negative integer, got %r" % (seed,))
+    if isinstance(init, str):
+        if init not in CLUSTER_INITS:
+            raise ValueError("init must be one of %s or an [n_clusters, dim] array, got %r" % (CLUSTER_INITS, init))
+    else:
+        init = np.array(init, dtype=np.float32, order="C")
+        if init.ndim != 2 or init.shape[0] != n_clusters or (dim and init.shape[1] != dim):
+            raise ValueError("an init array must be [n_clusters = %d, dim = %d], got shape %r"
+                             % (n_clusters, dim or 0, init.shape))
+        if not np.isfinite(init).all():
+            raise ValueError("an init array must be finite")
+    return int(n_clusters), int(max_iter), init
+
+
 def _check_score_threshold(score_threshold):
     if isinstance(score_threshold, bool) or not isinstance(score_threshold, (int, float, np.integer, np.floating)) \
             or math.isnan(score_threshold):
@@ -877,6 +973,7 @@ class HipChroma(VectorStoreBase):
         self._group_absent = None      # ((key, codes version), some row lacks the key)
         self._range_scratch = None     # the range search's device scratch, grown on demand
         self._join_scratch = None      # the self-join's device scratch, grown on demand
+        self._kmeans_scratch = None    # the k-means scratch, grown on demand
         if search_precision not in SEARCH_PRECISIONS:
             raise ValueError("search_precision must be one of %s, got %r"
                              % (sorted(SEARCH_PRECISIONS), search_precision))
@@ -1662,6 +1759,97 @@ class HipChroma(VectorStoreBase):
         if gone:
             self.delete(gone)
         return out
+
+    # ---- clustering: k-means over the store's rows ------------------------------------------
+    def _kmeans_room(self, n, n_clusters):
+        """The k-means scratch: grows on demand and is kept."""
+        import torch
+        need = kmeans_scratch_bytes(n, n_clusters)
+        if self._kmeans_scratch is None or self._kmeans_scratch.numel() < need:
+            self._kmeans_scratch = None  # release before growing
+            with _lib.device_scope(self._device):
+                self._kmeans_scratch = torch.empty(need, dtype=torch.uint8, device=torch.device("cuda", self._device))
+        return self._kmeans_scratch
+
+    def _cluster_run(self, n_clusters, max_iter, init, seed, ids, filter, where_document):
+        """-> (ClusterResult, device mask or None, admitted rows ascending): the checks, the mask
+        (`ids` ANDed with the filters), the seeding and one mq_index_kmeans call."""
+        if where_document is not None:
+            _check_where_document(where_document)
+        n_clusters, max_iter, init = _check_cluster_args(n_clusters, max_iter, init, seed, self._dim)
+        n = 0 if self._index is None else len(self._index)
+        if n and (self._dim % 64 or self._dim > 1024):
+            raise ValueError("clustering serves stores of dim %% 64 == 0, dim <= 1024 (this store's dim is %d)"
+                             % self._dim)
+        bits, admitted = None, np.ones(n, bool)
+        if n and (filter or where_document is not None):
+            _, bits = self._admit(1, filter, where_document)
+            admitted = np.asarray(self._mask_rows(bits), bool)
+        if ids is not None:
+            want = [ids] if isinstance(ids, str) else ids
+            named = np.zeros(n, bool)
+            named[[self._id_row.row(str(i)) for i in want if str(i) in self._id_row]] = True
+            admitted = admitted & named
+            bits = self._host_bits(admitted) if n else None
+        adm = np.flatnonzero(admitted)
+        if len(adm) < n_clusters:
+            raise ValueError("n_clusters=%d exceeds the %d rows the filters admit" % (n_clusters, len(adm)))
+        room = self._kmeans_room(n, n_clusters)
+        if isinstance(init, str):
+            rng = np.random.default_rng(seed)
+            if init == "random":
+                seeds = rng.choice(adm, n_clusters, replace=False)
+            else:
+                def dots_of_row(p):
+                    return self._index.kmeans(self._index.get(int(adm[p]), 1), 0, bits, room)[2][adm]
+                seeds = adm[kmeanspp_rows(len(adm), n_clusters, rng, dots_of_row)]
+            init = self._index.select(np.asarray(seeds, np.int64)).get()
+        cent, assign, dots, counts, info = self._index.kmeans(init, max_iter, bits, room)
+        labels = assign[adm]
+        c2 = (cent.astype(np.float64) ** 2).sum(1)
+        inertia = float((1.0 - 2.0 * dots[adm].astype(np.float64) + c2[labels]).sum())
+        res = ClusterResult([self._ids[r] for r in adm.tolist()], labels, cent, counts, info[0], info[1] == 0, inertia)
+        return res, bits, adm
+
+    def cluster(self, n_clusters=5, max_iter=25, init="k-means++", seed=0, ids=None, filter=None,
+                where_document=None):
+        """K-means over the store's rows (LangChain's `EmbeddingsClusteringFilter`, at the scale of
+        the store): Lloyd iterations on the device in exact fp32 (mq_index_kmeans, the definition:
+        include/mq.h "K-means") -> a `ClusterResult`.  The rows are those `filter` /
+        `where_document` admit and, with `ids`, those documents only (for example a range search's
+        hits).  init: an [n_clusters, dim] array of centres, "random" (default_rng(seed).choice of
+        the admitted rows, without replacement) or "k-means++" (`kmeanspp_rows`; every draw costs
+        one pass over the rows).  max_iter = 0 with an array init only labels the rows against the
+        given centres.  Fewer admitted rows than n_clusters raise ValueError.  Deterministic: the
+        same store, arguments and seed give the same bits."""
+        return self._cluster_run(n_clusters, max_iter, init, seed, ids, filter, where_document)[0]
+
+    def cluster_representatives(self, n_clusters=5, num_closest=1, sorted=False, remove_duplicates=False,
+                                **cluster_kwargs):
+        """The documents nearest each cluster centre: LangChain's `EmbeddingsClusteringFilter
+        .transform_documents` over the store.  After `cluster(n_clusters, **cluster_kwargs)` the
+        clusters are walked in order, each with the admitted rows ranked by nearness to its centre
+        (cosine descending, ties in insertion order - for unit rows the Euclidean order LangChain
+        sorts by).  With remove_duplicates: the first num_closest of the ranking, minus those
+        already taken.  Without it: the first num_closest of the ranking not already taken.  The
+        documents come in pick order, or in insertion order when `sorted` (`pick_representatives`).
+        The rankings are one range search with the centres as queries under the same mask, of
+        min(n_clusters x num_closest, admitted rows) entries each - enough, since at most
+        (n_clusters - 1) x num_closest rows are taken earlier; past MQ_RANGE_MAX_HITS it raises."""
+        if isinstance(num_closest, bool) or not isinstance(num_closest, (int, np.integer)) or num_closest < 1:
+            raise ValueError("num_closest must be a positive integer, got %r" % (num_closest,))
+        res, bits, adm = self._cluster_run(n_clusters, cluster_kwargs.pop("max_iter", 25),
+                                           cluster_kwargs.pop("init", "k-means++"), cluster_kwargs.pop("seed", 0),
+                                           cluster_kwargs.pop("ids", None), cluster_kwargs.pop("filter", None),
+                                           cluster_kwargs.pop("where_document", None))
+        if cluster_kwargs:
+            raise TypeError("unexpected arguments %s" % list(cluster_kwargs))
+        hits = _check_limit(int(n_clusters) * int(num_closest), len(adm))
+        n = len(self._index)
+        _, _, rows = self._index.search_range(res.centroids, hits, -math.inf, bits,
+                                              self._range_room(n, len(res.centroids), hits))
+        picks = pick_representatives([r[r >= 0] for r in rows], int(num_closest), bool(remove_duplicates), bool(sorted))
+        return [self._doc(r) for r in picks]
 
     # ---- lexical (BM25) and hybrid (reciprocal rank fusion) retrieval ----------------------
     def _lex_tok(self):
